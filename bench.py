@@ -2,7 +2,7 @@
 """Headline benchmark: rendered rays/sec, 64 coarse + 128 fine samples (the fine pass evaluates the merged
 192), 4096 synthetic rays per GPU (BASELINE.json configs[1]).
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20 [--full] [--dump-outputs DIR]
   python bench.py --gpus N ...                 (WORLD_SIZE unset: starts the N ranks itself -- see self_launch_command -- and relays rank 0's line)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W [--scaling weak] [--mode train]
@@ -15,8 +15,12 @@ The only collectives of the render mode are the barrier and the MAX of the timed
   --mode train     the line's metric becomes training rays/sec: rendering() drop-in forward + backward on this rank's
                    shard of a live-path batch (2000 rays x 90 cascade samples per GPU), ONE flat-bucket all-reduce of the
                    gradients over RCCL (parallel.FlatGradBucket, 0.73 MB), Adam step.
-In render mode with N > 1 a short data-parallel training run is appended as the secondary field `train_dp`, so that the
-RCCL bucket all-reduce is exercised and timed whenever the driver runs the scaling series.
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds, after the headline, the secondary measurements
+(other precisions, routes and sizes, the drop-in and training steps), the parity check against the CPU oracle and the CPU baseline; in
+render mode with N > 1 it adds the step under the other scaling rule and a short data-parallel training run as the secondary field
+`train_dp`, so that the RCCL bucket all-reduce is exercised and timed.
+--dump-outputs DIR writes what the last timed step returned (rank 0's rays) to DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -177,6 +181,32 @@ def guarded(fn, key=None):
     except Exception as e:       # noqa: BLE001
         err = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         return {key: err} if key else err
+
+
+def dump_outputs(path, out, limit_bytes=64 << 20, seed=0):
+    """--dump-outputs: every tensor of render()'s result as path/<name>.npy (a nested dict's entries as <key>.<name>), floating point as float32,
+    integers as float64 (exact).  Should they come to more than `limit_bytes` in all, each array keeps the same fixed, seeded sample of its rows
+    (dim 0) instead, so that two builds run with the same arguments still compare element for element."""
+    arrays = {}
+
+    def walk(prefix, d):
+        for k, v in d.items():
+            if isinstance(v, dict):
+                walk(prefix + k + ".", v)
+            elif torch.is_tensor(v):
+                arrays[prefix + k] = v.detach().to("cpu", torch.float32 if v.is_floating_point() else torch.float64)
+    walk("", out)
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    if total > limit_bytes:
+        frac = limit_bytes / total
+        for k, a in arrays.items():
+            if a.dim() > 0 and a.shape[0] > 1:
+                rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(seed))[:max(1, int(a.shape[0] * frac))]
+                arrays[k] = a[rows.sort()[0]]
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a.numpy())
 
 
 # ------------------------------------------------------------------------------------------------ sources as a real producer writes them
@@ -508,14 +538,22 @@ def main():
     ap.add_argument("--max-blocks", type=int, default=0)
     ap.add_argument("--fused-min-rounds", type=int, default=0,
                     help="bf16x3_fused: passes with fewer tiles per wave than this take the two-kernel route (0: always the fused kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements (other precisions, routes and sizes, the drop-in and training "
+                         "steps, N > 1: the other scaling rule and train_dp), the parity check against the CPU oracle and the CPU baseline; "
+                         "without it a run sets up, warms up, times --steps steps and prints the line")
     ap.add_argument("--no-reuse", "--headline-only", dest="no_reuse", action="store_true",
-                    help="skip the secondary measurements: profiling runs")
+                    help="with --full: skip the secondary measurements (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="render mode: write what the timed path returned in its last timed step to DIR/<name>.npy (rank 0's rays; see dump_outputs)")
     ap.add_argument("--graph", action="store_true", help="replay the step as one captured HIP graph (no per-kernel HIP events)")
     ap.add_argument("--precision", choices=["f32", "bf16x3", "bf16", "bf16x3_fused"], default="bf16x3_fused",
                     help="MLP arithmetic: exact fp32 MFMA; split-bf16 (3 bf16 MFMAs per product, fp32 accumulate, within the "
                          "1e-4 parity bar); plain bf16 (1 MFMA per product, NOT within the parity bar: PSNR reported); bf16x3_fused (default): "
                          "split-bf16 with the feature gather inside the MLP kernel -- one launch per pass, no feature buffer")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "render":
+        ap.error("--dump-outputs: render mode only")
     self_launch(args.gpus, sys.argv[1:])          # N > 1 without a launcher: start the ranks (this process then only relays and exits)
     ctx = Ctx(args)
     rank, world, dev = ctx.rank, ctx.world, ctx.dev
@@ -580,6 +618,8 @@ def main():
     barrier()
     dt = ctx.max_over_ranks(time.perf_counter() - t0)
     assert torch.isfinite(out["rgb"]).all() and torch.isfinite(out["depth"]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # dominant kernel (mlp_fwd): HIP events recorded around its two launches per step, on the launch stream
     mlp_ms = sum(a.elapsed_ms(b) for step in events for a, b in step)
@@ -597,7 +637,7 @@ def main():
         if not line_once.acquire(blocking=False):      # (the watchdog and the main thread never both print)
             return
         psnr_vs_f32 = None
-        if args.precision == "bf16" and final:         # outside the parity bar by construction: report the distance to the exact render
+        if args.precision == "bf16" and args.full and final:         # outside the parity bar by construction: report the distance to the exact render
             r32 = CoarseFineRenderer(scene, flat_params_of(sd).to(dev), args.coarse, args.fine, precision="f32")
             ref = r32.pass_(out["rays_d"], out["z_fine"])            # same fine depths: isolates the network arithmetic
             mse = torch.mean((out["rgb"] - ref["rgb"]) ** 2).item()
@@ -668,7 +708,7 @@ def main():
             if psnr_vs_f32 is not None:
                 line["parity_vs_f32"] = psnr_vs_f32
             line.update(extra_)
-            if args.cpu_rays > 0 and world == 1 and final:      # (N = 1 only: the CPU legs take 10-30 s, during which other ranks would sit at the closing barrier)
+            if args.full and args.cpu_rays > 0 and world == 1 and final:      # (N = 1 only: the CPU legs take 10-30 s, during which other ranks would sit at the closing barrier)
                 line["parity_vs_oracle"] = guarded(lambda: parity_vs_oracle(scene_cpu, sd, out, xs_all[:rays], ys_all[:rays], noise.cpu(), args.coarse, args.fine))
                 line["cpu_baseline"] = cpu_baseline(scene_cpu, sd, args.cpu_rays, args.coarse, args.fine)
             print(json.dumps(line), flush=True)
@@ -689,7 +729,7 @@ def main():
         threading.Thread(target=watchdog, daemon=True).start()
 
     extra = {}
-    secondary = not args.no_reuse
+    secondary = args.full and not args.no_reuse
     if secondary:
         # reuse_coarse: the fine pass evaluates only the 128 new depths (bit-identical renders, tests/test_hip_pipeline.py)
         def reuse():

@@ -16,6 +16,8 @@ an exact description of what to compute.
 """
 import torch
 
+from .ucnerf_oracle import matmul3
+
 
 def create_meshgrid_pixels(H, W, dtype=torch.float32):
     """kornia.utils.create_meshgrid(H, W, normalized_coordinates=False): [1,H,W,2], last dim = (x, y)."""
@@ -37,7 +39,7 @@ def homo_warp_grid(proj_mat, depth_values, H, W, pad=0):
     g = grid.permute(0, 3, 1, 2).reshape(1, 2, Hp * Wp)
     g = torch.cat((g, torch.ones_like(g[:, :1])), 1)                     # [1,3,Hp*Wp]
     g = g.repeat(1, 1, D)                                                # [1,3,D*Hp*Wp]
-    q = R.unsqueeze(0) @ g + T.unsqueeze(0) / depth_values.reshape(1, 1, D * Hp * Wp)
+    q = matmul3(R.unsqueeze(0), g) + T.unsqueeze(0) / depth_values.reshape(1, 1, D * Hp * Wp)
     xy = q[:, :2] / q[:, 2:]
     x = xy[:, 0] / ((W - 1) / 2) - 1
     y = xy[:, 1] / ((H - 1) / 2) - 1

@@ -27,10 +27,41 @@ Reference locations restated (paths relative to the reference tree):
   a9  network/renderer.py:6-36 and :109-140, utils/run_nerf_helpers.py:343-390
   a10 network/renderer.py:215-255, data/ray_utils.py:199-224 (coarse->fine recipe)
 """
+import contextlib
 import math
 
 import numpy as np
 import torch
+
+
+_FUSED_CAMERA_PRODUCTS = False
+
+
+def matmul3(a, b):
+    """a @ b for the camera products (a contraction over 3: a [..., M, 3], b [..., 3, N]) in elementwise operations, so that the bits do not
+    depend on the kernel a BLAS picks for the processor.  float32: k ascending, each product rounded and then added, as the HIP kernels
+    (-ffp-contract=off) and MKL's generic code path compute it; inside fused_camera_products(), as MKL's AVX-512 path computes it on the host the
+    golden vectors were captured on: fma(a2, b2, fma(a1, b1, a0 * b0)), each fused step the exact product summed in float64 and rounded to float32."""
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        return a @ b
+    acc = a[..., 0:1] * b[..., 0:1, :]
+    for k in (1, 2):
+        if _FUSED_CAMERA_PRODUCTS:
+            acc = (a[..., k:k + 1].double() * b[..., k:k + 1, :].double() + acc.double()).float()
+        else:
+            acc = acc + a[..., k:k + 1] * b[..., k:k + 1, :]
+    return acc
+
+
+@contextlib.contextmanager
+def fused_camera_products():
+    """matmul3 rounds as MKL did on the host the golden vectors were captured on (tests/test_oracle_golden.py)."""
+    global _FUSED_CAMERA_PRODUCTS
+    prev, _FUSED_CAMERA_PRODUCTS = _FUSED_CAMERA_PRODUCTS, True
+    try:
+        yield
+    finally:
+        _FUSED_CAMERA_PRODUCTS = prev
 
 # --------------------------------------------------------------------------------------------
 # a1  ray generation
@@ -56,7 +87,7 @@ def get_ray_directions(H, W, K):
 
 def get_rays(directions, c2w):
     """rays_d = dirs @ R^T (not normalised), rays_o = t broadcast (data/ray_utils.py:45-51)."""
-    rays_d = (directions.reshape(-1, 3) @ c2w[:3, :3].T)
+    rays_d = matmul3(directions.reshape(-1, 3), c2w[:3, :3].T)
     rays_o = c2w[:3, 3].expand_as(rays_d)
     return rays_o, rays_d
 
@@ -72,7 +103,7 @@ def get_rays_mvs_grid(H, W, K, c2w, chunk=-1, idx=-1):
 
 def get_rays_mvs_pixels(xs, ys, K, c2w):
     """get_rays_mvs on given pixel coordinates (the random branches differ only in how xs, ys are drawn)."""
-    rays_d = camera_dirs(xs, ys, K) @ c2w[:3, :3].T
+    rays_d = matmul3(camera_dirs(xs, ys, K), c2w[:3, :3].T)
     rays_o = c2w[:3, -1].clone()
     return rays_o, rays_d, torch.stack((ys, xs))
 
@@ -174,10 +205,10 @@ def project_points(w2c, K, pts, inv_scale):
     shp = pts.shape
     p = pts.reshape(-1, 3)
     if w2c is not None:
-        p = p @ w2c[:3, :3].T + w2c[:3, 3].reshape(1, 3)
+        p = matmul3(p, w2c[:3, :3].T) + w2c[:3, 3].reshape(1, 3)
         z = torch.where(p[:, 2].abs() < 1e-4, torch.full_like(p[:, 2], 1e-4), p[:, 2])
         p = torch.stack([p[:, 0], p[:, 1], z], -1)
-    q = p @ K.T
+    q = matmul3(p, K.T)
     xy = (q[:, :2] / q[:, 2:] + 0.0) / inv_scale.reshape(1, 2).to(q.dtype)
     return torch.cat([xy, q[:, 2:]], -1).reshape(shp)
 
@@ -387,7 +418,7 @@ def gen_pts_feats(imgs, vols, pts, w2cs, intrinsics, ndc, img_feat, confidence):
 
 def gen_dir_feature(w2c_ref, rays_dir):
     """network/renderer.py:163-174."""
-    return rays_dir @ w2c_ref[:3, :3].T
+    return matmul3(rays_dir, w2c_ref[:3, :3].T)
 
 
 # --------------------------------------------------------------------------------------------

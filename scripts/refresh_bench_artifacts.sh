@@ -3,7 +3,9 @@
 set -e
 R=$GRAFT_REPO_ROOT
 cd $R
-python bench.py > gpurun_out/final_bf16x3_fused.json 2> gpurun_out/final_bf16x3_fused.err
+# OUT: the directory the artifacts of this script go to, the one scripts/collect_profiles.sh reads
+OUT=${OUT:?set OUT to the artifact directory}
+python bench.py --full > $OUT/final_bf16x3_fused.json 2> $OUT/final_bf16x3_fused.err
 python bench.py --precision f32 --cpu-rays 0 --no-reuse > gpurun_out/final_f32.json 2> gpurun_out/final_f32.err
 cd /tmp && export TMPDIR=/tmp
 for v in bf16x3_fused bf16x3 f32; do
@@ -27,7 +29,7 @@ python scripts/pmc_by_kernel.py gpurun_out/final_pmc_train gpurun_out/final_trai
 bash scripts/prof_strong.sh final > gpurun_out/final_strong512.log 2>&1 || true
 bash scripts/prof_dropin_train.sh final > gpurun_out/final_dropin_train_trace.log 2>&1 || true
 # the data-parallel step through a ONE-rank RCCL group (the collective's code path on one GPU)
-UCNERF_BENCH_GROUP_AT_1=1 python bench.py --cpu-rays 0 2> gpurun_out/final_rccl1.err | grep '^{' > gpurun_out/final_rccl1.json || true
+UCNERF_BENCH_GROUP_AT_1=1 python bench.py --full --cpu-rays 0 2> $OUT/final_rccl1.err | grep '^{' > $OUT/final_rccl1.json || true
 # the self-launched four-rank line (all ranks on this GPU, gloo for the collective; six processes at most may share the card): only the JSON line is kept
-UCNERF_BENCH_BACKEND=gloo python bench.py --gpus 4 --steps 20 --warmup 5 2> gpurun_out/final_n4_gloo.err | grep '^{' > gpurun_out/final_n4_gloo.json || true
-tail -c 300 $R/gpurun_out/final_bf16x3_fused.json
+UCNERF_BENCH_BACKEND=gloo python bench.py --full --gpus 4 --steps 20 --warmup 5 2> $OUT/final_n4_gloo.err | grep '^{' > $OUT/final_n4_gloo.json || true
+tail -c 300 $OUT/final_bf16x3_fused.json

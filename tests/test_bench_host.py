@@ -50,3 +50,29 @@ def test_self_launch_spawns_the_ranks_and_relays_their_exit_code(tmp_path):
     assert r.stdout.count("LINE from rank 0 of 2 ['--steps', '3']") == 1, r.stdout
     r = subprocess.run([sys.executable, str(script), "--fail"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
+
+
+def test_dump_outputs_writes_every_tensor_and_keeps_a_fixed_sample_above_the_limit(tmp_path):
+    """--dump-outputs: each tensor of render()'s result (nested dicts flattened to <key>.<name>) as float32 / float64 .npy; above the size limit
+    every array keeps the same seeded rows, so two runs (or two builds) compare element for element."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(1)
+    out = {"rgb": torch.rand(64, 3, generator=g), "depth": torch.rand(64, generator=g, dtype=torch.float64), "note": None,
+           "coarse": {"weights": torch.rand(64, 8, generator=g).half(), "rank": torch.arange(64 * 8, dtype=torch.int32).view(64, 8)}}
+    b.dump_outputs(str(tmp_path / "all"), out)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert sorted(got) == ["coarse.rank", "coarse.weights", "depth", "rgb"]
+    assert got["rgb"].dtype == np.float32 and np.array_equal(got["rgb"], out["rgb"].numpy())
+    assert got["depth"].dtype == np.float32 and np.array_equal(got["coarse.weights"], out["coarse"]["weights"].float().numpy())
+    assert got["coarse.rank"].dtype == np.float64 and np.array_equal(got["coarse.rank"], out["coarse"]["rank"].numpy())
+    # a quarter of the bytes allowed: a quarter of the rows, the same rows in every array and in every run
+    total = sum(a.nbytes for a in got.values())
+    for run in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / run), out, limit_bytes=total // 4)
+    s1 = {p.stem: np.load(p) for p in (tmp_path / "s1").iterdir()}
+    assert sum(a.nbytes for a in s1.values()) <= total // 4
+    assert all(np.array_equal(a, np.load(tmp_path / "s2" / (k + ".npy"))) for k, a in s1.items())
+    rows = [i for i in range(64) if (s1["rgb"] == got["rgb"][i]).all(-1).any()]
+    assert len(rows) == 16 and np.array_equal(s1["depth"], got["depth"][rows]) and np.array_equal(s1["coarse.rank"], got["coarse.rank"][rows])

@@ -4,6 +4,7 @@
 #include "raygen_device.h"
 
 #include <atomic>
+#include <climits>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -417,6 +418,7 @@ int ucnerf_ray_gen(const ucnerf_ray_gen_params* p, void* stream) {
     UCNERF_REQUIRE(p, "ray_gen: null params");
     UCNERF_REQUIRE(p->n >= 0, "ray_gen: n < 0");
     if (p->n == 0) return UCNERF_OK;
+    UCNERF_REQUIRE(p->n <= INT_MAX / 3, "ray_gen: %d rays overflow the int indexing of the [n,3] outputs", p->n);
     UCNERF_REQUIRE(p->rays_d, "ray_gen: null rays_d");
     UCNERF_REQUIRE((p->xs == nullptr) == (p->ys == nullptr), "ray_gen: xs and ys must both be given or both NULL");
     UCNERF_REQUIRE(p->xs || (p->W > 0 && p->H > 0 && p->grid_start >= 0 &&
@@ -431,6 +433,7 @@ int ucnerf_ray_gen_sample(const ucnerf_ray_gen_params* rg, const ucnerf_sample_s
     UCNERF_REQUIRE(rg && ss, "ray_gen_sample: null params");
     UCNERF_REQUIRE(rg->n == ss->n && rg->n >= 0, "ray_gen_sample: %d rays but depths for %d", rg->n, ss->n);
     if (rg->n == 0) return UCNERF_OK;
+    UCNERF_REQUIRE(rg->n <= INT_MAX / 3, "ray_gen_sample: %d rays overflow the int indexing of the [n,3] outputs", rg->n);
     UCNERF_REQUIRE(rg->rays_d && ss->z && ss->S >= 1, "ray_gen_sample: null rays_d / z or S < 1");
     UCNERF_REQUIRE((rg->xs == nullptr) == (rg->ys == nullptr), "ray_gen_sample: xs and ys must both be given or both NULL");
     UCNERF_REQUIRE(rg->xs || (rg->W > 0 && rg->H > 0 && rg->grid_start >= 0 && (long long)rg->grid_start + rg->n <= (long long)rg->H * rg->W),
