@@ -8,16 +8,12 @@
 #include "mlp_layout.h"
 #include "p24.h"
 #include "sincos_cw.h"
+#include "mfma_split.h"
 
 #include <cstdlib>
 #include <vector>
 
 namespace ucnerf {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef UCNERF_MLP_WAVES
 #define UCNERF_MLP_WAVES 8
@@ -156,8 +152,6 @@ struct MlpGeom {      // MlpLayout subset the kernel needs (32-bit is plenty: th
     int stagger;          // start-up delay of waves 4..7 in units of s_sleep(127) (= 8128 cycles)
 };
 
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-
 // The weight stream is walked strictly in order by every wave.  It is addressed as a buffer: the descriptor and
 // the running k-step offset `soff` live in SGPRs, the per-lane part (lane*16 bytes) in one VGPR, so a load costs
 // no VALU address arithmetic.  `ring` holds the next RING k-steps already in flight; sched_barrier(0) after each
@@ -178,10 +172,10 @@ __device__ __forceinline__ f32x4 load_kstep(const Stream& S, int rel) {
         const f32x4 a_ = (S).ring[(T) & (RING - 1)];             \
         (S).ring[(T) & (RING - 1)] = load_kstep((S), (T) + RING);\
         const float b_ = (BVAL);                                 \
-        (ACC)[0] = MFMA(a_.x, b_, (ACC)[0]);                     \
-        (ACC)[1] = MFMA(a_.y, b_, (ACC)[1]);                     \
-        (ACC)[2] = MFMA(a_.z, b_, (ACC)[2]);                     \
-        (ACC)[3] = MFMA(a_.w, b_, (ACC)[3]);                     \
+        (ACC)[0] = mfma_32x32x2(a_.x, b_, (ACC)[0]);             \
+        (ACC)[1] = mfma_32x32x2(a_.y, b_, (ACC)[1]);             \
+        (ACC)[2] = mfma_32x32x2(a_.z, b_, (ACC)[2]);             \
+        (ACC)[3] = mfma_32x32x2(a_.w, b_, (ACC)[3]);             \
         __builtin_amdgcn_sched_barrier(0);                       \
     }
 
@@ -352,7 +346,7 @@ constexpr int XPOSE_BYTES = 32 * XPOSE_ROW;
 template <bool P24>
 __device__ __forceinline__ void save_rows(float* buf, int s, int h, bool valid, const f32x16 (&x)[4], char* xbuf = nullptr, int lane = 0, int tile = 0, int m = 0) {
     if (P24) {
-        asm volatile("" : "+v"(lane));                // (the chunk addresses below do not depend on the tile: unlaundered they are hoisted out of the tile loop -- 24 registers for the whole kernel)
+        lane = opaque(lane);                          // (the chunk addresses below do not depend on the tile: unlaundered they are hoisted out of the tile loop -- 24 registers for the whole kernel)
         const int j = lane & 31;
         char* const gtile = reinterpret_cast<char*>(buf) + (size_t)tile * 32 * P24_ROW_BYTES;
         const int rows = m - tile * 32;               // valid rows of this tile (>= 32: all)

@@ -37,9 +37,7 @@
 #include "p24.h"
 #include "composite_device.h"
 #include "sample_pdf_device.h"
-
-// the LDS-DMA asm below names m0 as a clobber on purpose (it loads the LDS base into it)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "mfma_split.h"
 
 #include <cstdlib>
 #include <vector>
@@ -57,9 +55,6 @@
 
 namespace ucnerf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // ucnerf_mlp_config.operand (ABI v6): every build of this file exists twice -- with bf16 terms (UCNERF_OPERAND_FP16 = 0: the entry points below) and with
 // fp16 terms (UCNERF_OPERAND_FP16 = 1: 11-bit hi and lo terms, v_mfma_f32_32x32x16_f16; the same entry points under the suffix _h16, which the
 // bf16 build's entry points forward to when cfg.operand == 1).  fp16 has no range guard: values beyond 65 504 overflow.
@@ -92,7 +87,7 @@ typedef _Float16 op16;
 #else
 typedef __bf16 op16;
 #endif
-typedef op16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef op16 op16x8 __attribute__((ext_vector_type(8)));      // an operand fragment: bf16x8 or f16x8 (mfma_32x32x16 takes either)
 
 #ifndef UCNERF_BF16_HINT_V
 #define UCNERF_BF16_HINT_V 5   // VALU instructions the scheduler may place after each MFMA of a half-step (7 would fill an MFMA's 32 cycles; measured
@@ -104,17 +99,6 @@ typedef op16 bf16x8 __attribute__((ext_vector_type(8)));
 #ifndef UCNERF_BF16_PRIO_GEMM
 #define UCNERF_BF16_PRIO_GEMM 0     // ... and during the GEMM phases
 #endif
-// scalar fp32 ops the SLP vectoriser cannot re-pack (one empty asm per result keeps every op its own instruction)
-__device__ __forceinline__ float sc_mul(float a, float b) { float r = a * b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float sc_sub(float a, float b) { float r = a - b; asm volatile("" : "+v"(r)); return r; }
-__device__ __forceinline__ float sc_fma(float a, float b, float c) { float r = __builtin_fmaf(a, b, c); asm volatile("" : "+v"(r)); return r; }
-#if UCNERF_OPERAND_FP16
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-#else
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#endif
-#define SB0 __builtin_amdgcn_sched_barrier(0)
-
 #ifndef UCNERF_BF16_IDLE_SKIP
 #define UCNERF_BF16_IDLE_SKIP 1          // a wave whose tile lies past the end only turns the weight ring (0: it computes a clamped tile and discards it)
 #endif
@@ -147,9 +131,6 @@ static bool bf16_layout(int v, Bf16Layout* B) {
     B->total_bytes = B->const_off_bytes + (int64_t)CONST_FLOATS * 4;
     return true;
 }
-
-// feature held by element j of lane-half hh in hidden k16-step q = (kt, s): accumulator register 8s + j of row-tile kt
-__host__ __device__ inline int hid_feature16(int kt, int s, int j, int hh) { return 32 * kt + (j & 3) + 8 * (2 * s + (j >> 2)) + 4 * hh; }
 
 #if UCNERF_BF16_BUILD_TERMS == 3 && !UCNERF_BF16_BUILD_TAIL
 // ------------------------------------------------------------------------------------------------ host: pack index
@@ -253,7 +234,7 @@ int build_pack_index_bf16(const ucnerf_mlp_config* cfg, int32_t* idx) {
 #endif   // UCNERF_BF16_BUILD_TERMS == 3 (host-side packing)
 
 // ------------------------------------------------------------------------------------------------ device helpers
-struct Frag { bf16x8 hi, lo; };
+typedef HiLo<op16x8> Frag;
 
 // (hi, lo) split of eight activations: hi = bf16_rne(x), lo = bf16_rne(x - hi) (the difference is exact before its rounding): one v_cvt_pk_bf16_f32
 // per pair for each, a shift and a mask to read the pair's hi back as floats, one packed subtract -- 5 VALU per pair.  Worst case |lo| <= 2^-8 |x|,
@@ -262,14 +243,12 @@ struct Frag { bf16x8 hi, lo; };
 //  fuzzer, tests/fuzz_render.py, put the renders of that split at up to 2.5e-4 from the oracle on networks with an unscaled density head --
 //  4 of 43 such cases above the 1e-4 bar; with the rounded hi the median error halves (2.9e-5 -> 1.9e-5, 90th percentile 9.3e-5 -> 4.7e-5)
 //  for +0.2 % of the headline kernel's time, profiles/r05_experiments.md.)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef op16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef op16 op16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ Frag split8(const float (&x)[8]) {
     u32x4 hi;
     Frag f;
 #if UCNERF_OPERAND_FP16 && !UCNERF_BF16_BUILD_TAIL
-    float minus_one = -1.0f;
-    asm volatile("" : "+s"(minus_one));
+    const float minus_one = sopaque(-1.0f);
 #endif
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -295,7 +274,7 @@ __device__ __forceinline__ Frag split8(const float (&x)[8]) {
         f.lo[j] = (op16)lp[0];
         f.lo[j + 1] = (op16)lp[1];
 #else
-        const bf16x2 hp = __builtin_convertvector((f32x2){x[j], x[j + 1]}, bf16x2);      // ONE v_cvt_pk_bf16_f32 (two scalar conversions were not merged)
+        const op16x2 hp = __builtin_convertvector((f32x2){x[j], x[j + 1]}, op16x2);      // ONE v_cvt_pk_bf16_f32 (two scalar conversions were not merged)
         const unsigned packed = __builtin_bit_cast(unsigned, hp);                 // [hi(x[j+1]) | hi(x[j])]
         hi[j >> 1] = packed;
         const f32x2 h = {__builtin_bit_cast(float, packed << 16), __builtin_bit_cast(float, packed & 0xffff0000u)};
@@ -304,19 +283,9 @@ __device__ __forceinline__ Frag split8(const float (&x)[8]) {
         f.lo[j + 1] = (op16)l.y;
 #endif
     }
-    f.hi = __builtin_bit_cast(bf16x8, hi);
+    f.hi = __builtin_bit_cast(op16x8, hi);
     return f;
 }
-
-// (The constants never change, so the compiler would hoist these LDS loads out of the tile loop and then spill what it
-//  hoisted: the lane offset is laundered through an empty asm to keep every load where it is written.)
-__device__ __forceinline__ int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// the same for a wave-uniform value (kept in a scalar register); `on` = 0: identity (inside a GEMM phase's fill the asm form does not select:
-// "illegal VGPR to SGPR copy")
-__device__ __forceinline__ int sopaque(int v, bool on = true) { if (on) asm volatile("" : "+s"(v)); return v; }
-// Results that are only needed much later would be sunk towards their use -- out of the MFMA shadow they were written
-// for, with their operands kept live meanwhile.  An empty volatile asm on the result pins the arithmetic in place.
-template <class T> __device__ __forceinline__ void pin(T& v) { asm volatile("" : "+v"(v)); }
 
 // Training forward (SAVE): the activation sets the backward reads (MlpSaved, mlp_layout.h), row-major [m,128].  A lane owns 64 of its
 // sample's 128 values per set: register group (nt, q = reg / 4) of lane-half h sits at floats 32 nt + 8 q + 4 h of the row.
@@ -369,7 +338,7 @@ struct BGeom {
 };
 
 // A fragments of one half-step (row-tile pair)
-struct AF { bf16x8 h0, l0, h1, l1; };
+typedef PairFrags<op16x8> AF;
 
 // block-wide weight pipeline state (all values wave-uniform)
 struct Pipe {
@@ -383,21 +352,19 @@ struct Pipe {
     int slots;
 };
 
-// The copy is issued from inline asm on purpose: the compiler models a global_load_lds as a FLAT access that may
-// touch both memories and from then on degrades every counted wait of the kernel to vmcnt(0) / lgkmcnt(0), which
-// serialises the fragment prefetch below.  All hazards of the ring are handled explicitly in advance().
+// (lds_dma16: the compiler does not count these copies -- all hazards of the ring are handled explicitly in advance())
 template <int NB = NBUF>
 __device__ __forceinline__ void issue_dma(Pipe& P, int pos) {
+    static_assert(DMA_PER_SLOT == 1 || DMA_PER_SLOT == 2, "BW = 8 or 4 waves per ring");
     const char* src = P.gsrc + (size_t)P.next_src * SLOT_BYTES;
     const unsigned dst = P.ring_lds + (pos & (NB - 1)) * SLOT_BYTES + P.wave * (DMA_PER_SLOT * 1024);
-#pragma unroll
-    for (int i = 0; i < DMA_PER_SLOT; ++i)
-        asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off offset:%2" ::"v"(src), "s"(dst), "n"(i * 1024) : "memory", "m0");   // the offset moves both addresses
+    lds_dma16(src, dst);
+    if (DMA_PER_SLOT == 2) lds_dma16<1024>(src, dst);
     P.next_src = P.next_src + 1 == P.slots ? 0 : P.next_src + 1;
 }
 
 __device__ __forceinline__ AF read_half(const char* buf, int lane, int half) {
-    const bf16x8* a = reinterpret_cast<const bf16x8*>(buf + half * HALF_BYTES) + lane;
+    const op16x8* a = reinterpret_cast<const op16x8*>(buf + half * HALF_BYTES) + lane;
     AF f;
     f.h0 = a[0]; f.l0 = a[64]; f.h1 = a[128]; f.l1 = a[192];
     return f;
@@ -408,7 +375,7 @@ __device__ __forceinline__ AF read_half(const char* buf, int lane, int half) {
 // vmcnt: the DMAs younger than the awaited slot are those of the NBUF - 2 slots after it.
 template <int NB = NBUF>
 __device__ __forceinline__ void advance(Pipe& P) {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NB - 2) * DMA_PER_SLOT) : "memory");
+    wait_vmcnt_lgkmcnt<(NB - 2) * DMA_PER_SLOT>();
     __builtin_amdgcn_s_barrier();
     issue_dma<NB>(P, P.gpos);                               // position gpos + NB into the slot of position gpos
     ++P.gpos;
@@ -434,14 +401,14 @@ __device__ __forceinline__ void half_step(const int ODD, Pipe& P, AF& cur, int l
     AF nxt;
     if (TERMS == 3) nxt = read_half(P.buf, lane, ODD ? 0 : 1);
     else {                                                 // plain bf16: the lo halves are never read
-        const bf16x8* a = reinterpret_cast<const bf16x8*>(P.buf + (ODD ? 0 : 1) * HALF_BYTES) + lane;
+        const op16x8* a = reinterpret_cast<const op16x8*>(P.buf + (ODD ? 0 : 1) * HALF_BYTES) + lane;
         nxt.h0 = a[0]; nxt.h1 = a[128]; nxt.l0 = nxt.h0; nxt.l1 = nxt.h1;
     }
     SB0;
-    c0 = MFMA16(cur.h0, b.hi, c0);
-    if (TERMS == 3) { c0 = MFMA16(cur.h0, b.lo, c0); c0 = MFMA16(cur.l0, b.hi, c0); }   // (one accumulation chain runs at full rate)
-    c1 = MFMA16(cur.h1, b.hi, c1);
-    if (TERMS == 3) { c1 = MFMA16(cur.h1, b.lo, c1); c1 = MFMA16(cur.l1, b.hi, c1); }
+    c0 = mfma_32x32x16(cur.h0, b.hi, c0);
+    if (TERMS == 3) { c0 = mfma_32x32x16(cur.h0, b.lo, c0); c0 = mfma_32x32x16(cur.l0, b.hi, c0); }   // (one accumulation chain runs at full rate)
+    c1 = mfma_32x32x16(cur.h1, b.hi, c1);
+    if (TERMS == 3) { c1 = mfma_32x32x16(cur.h1, b.lo, c1); c1 = mfma_32x32x16(cur.l1, b.hi, c1); }
     fill();
     if (TERMS == 3) interleave_hint<UCNERF_BF16_HINT_V>();
     SB0;
@@ -636,7 +603,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
                 const size_t k = (size_t)ray0 * fg.S + i;
                 fg.gen_z[k] = stratified_depth(fg.near, fg.far, i % fg.S, fg.S, fg.gen_lindisp, fg.gen_perturb, fg.gen_noise ? fg.gen_noise[k] : 0.f);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         }
         if (TAIL && fg.tail_dir_Q) {
@@ -649,7 +616,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
                 view_dir_feature(fg.rays_d[o], fg.rays_d[o + 1], fg.rays_d[o + 2], fg.tail_dir_Q, &ax, &ay, &az);      // (dir_feature_kernel's arithmetic)
                 fg.tail_dir_out[o] = ax; fg.tail_dir_out[o + 1] = ay; fg.tail_dir_out[o + 2] = az;
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         }
         __syncthreads();
@@ -662,8 +629,8 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
     P.wave = wave; P.gpos = 0; P.next_src = 0; P.slots = g.slots;
 #pragma unroll
     for (int i = 0; i < NB; ++i) issue_dma<NB>(P, i);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NB - 1) * DMA_PER_SLOT) : "memory");       // slot 0 has landed ...
-    __builtin_amdgcn_s_barrier();                                                        // ... for every wave
+    wait_vmcnt<(NB - 1) * DMA_PER_SLOT>();                  // slot 0 has landed ...
+    __builtin_amdgcn_s_barrier();                           // ... for every wave
     AF cur = read_half(P.buf, lane, 0);                     // (TERMS 1 reads the unused lo halves once here)
 
     // Tile of (round, block, wave), WAVE-MAJOR inside a round: a last round that is only partly filled then keeps the same number of waves
@@ -1075,7 +1042,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         // One batch of plain loads per tile (confidence-net operands + view direction, issued under phase B below):
         // a compiler-counted wait cannot see the weight DMAs and so drains them -- once here instead of per load site.
         int s_here = sample_of(tile);
-        asm volatile("" : "+v"(s_here));                    // (re-derive the row pointer instead of carrying 64 bits through the trunk)
+        pin(s_here);                                        // (re-derive the row pointer instead of carrying 64 bits through the trunk)
         const float* fb = feat_base(s_here);
         const float* fhb = fb + 8 * opaque(h) * fstride;
         float dv[3];
@@ -1123,7 +1090,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
                            dv[0] = fg.gen_xs[r_]; dv[1] = fg.gen_ys[r_]; dv[2] = fg.gen_noise ? fg.gen_noise[s_here] : 0.f;
                        } else {
                        int ray = s_here;
-                       if (!p.dirs_per_sample) { int S = p.S; asm volatile("" : "+s"(S)); ray = s_here / S; }   // (opaque: no reciprocal hoisted into a loop-long VGPR)
+                       if (!p.dirs_per_sample) ray = s_here / sopaque(p.S);   // (opaque: no reciprocal hoisted into a loop-long VGPR)
                        const float* drow = p.dirs + (size_t)ray * 3;
                        dv[0] = drow[0]; dv[1] = drow[1]; dv[2] = drow[2];
                        }
@@ -1259,7 +1226,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         out.w = fmaxf(adapt.w * omu + base.w * u, 0.f);
         if (h == 0 && s_raw < s_lim) reinterpret_cast<f32x4*>(p.raw)[s_raw] = out;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // no LDS-DMA may outlive the workgroup's LDS allocation
+    wait_vmcnt<0>();       // no LDS-DMA may outlive the workgroup's LDS allocation
     if (TAIL) {
         // ---- K7 (+ K8, K9) of this block's rays.  Every output of every tile of these rays was stored by a wave of THIS block: the stores have been
         // acknowledged (vmcnt(0) above), the barrier orders them before the loads below, which miss the CU's vector cache (nobody has read these

@@ -12,12 +12,9 @@
 #include "common.h"
 #include "mlp_layout.h"
 #include "mlp_bwd_parts.h"
+#include "mfma_split.h"
 
 namespace ucnerf {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 int launch_mlp_fwd(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st);
 int launch_mlp_fwd_bf16x3_save(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st);      // mlp_bf16.hip
@@ -127,7 +124,7 @@ __global__ void __launch_bounds__(64 * NN_WAVES) gemm_nn_kernel(NnArgs a, int n_
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[nt] = MFMA(av[c], wk[(8 * q + c) * NP + 32 * nt], acc[nt]);
+                    for (int nt = 0; nt < NT; ++nt) acc[nt] = mfma_32x32x2(av[c], wk[(8 * q + c) * NP + 32 * nt], acc[nt]);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");          // the tile is rewritten next
             __builtin_amdgcn_wave_barrier();
@@ -200,28 +197,6 @@ struct TnArgs {
 
 template <int KT, int NE>
 struct TnStage { float g[NE], x[NE][KT]; };
-
-// split-bf16 operands for the bf16 matrix cores (same scheme as the forward's bf16x3 kernel, csrc/mlp_bf16.hip): x = hi + lo
-// with hi the truncated top 16 bits and lo = bf16_rne(x - hi); a product is hi*hi + hi*lo + lo*hi, the dropped term 2^-16.
-typedef __bf16 tn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned tn_u32x4 __attribute__((ext_vector_type(4)));
-typedef float tn_f32x2 __attribute__((ext_vector_type(2)));
-struct TnFrag { tn_bf16x8 hi, lo; };
-__device__ __forceinline__ TnFrag tn_split8(const float (&x)[8]) {
-    tn_u32x4 hi;
-    TnFrag f;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const unsigned b0 = __builtin_bit_cast(unsigned, x[j]), b1 = __builtin_bit_cast(unsigned, x[j + 1]);
-        hi[j >> 1] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        const tn_f32x2 l = (tn_f32x2){x[j], x[j + 1]} - (tn_f32x2){__builtin_bit_cast(float, b0 & 0xffff0000u), __builtin_bit_cast(float, b1 & 0xffff0000u)};
-        f.lo[j] = (__bf16)l.x;
-        f.lo[j + 1] = (__bf16)l.y;
-    }
-    f.hi = __builtin_bit_cast(tn_bf16x8, hi);
-    return f;
-}
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 // KT column tiles per wave, KSPLIT waves share a row tile (each with its own KT column tiles), DEPTH stages of loads in
 // flight ahead of the MFMAs.  16 waves = (4 / KSPLIT sample groups) x 4 row tiles x KSPLIT.
@@ -296,23 +271,23 @@ __global__ void __launch_bounds__(1024) gemm_tn_kernel(TnArgs a) {
                 float gv[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { gv[e] = st.g[e]; colsum += st.g[e]; }
-                const TnFrag gf = tn_split8(gv);
+                const HiLo<bf16x8> gf = split8_trunc(gv);
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt) {
                     float xv[8];
 #pragma unroll
                     for (int e = 0; e < 8; ++e) xv[e] = st.x[e][kt];
-                    const TnFrag xf = tn_split8(xv);
-                    acc[kt] = MFMA16(gf.hi, xf.hi, acc[kt]);
-                    acc[kt] = MFMA16(gf.hi, xf.lo, acc[kt]);
-                    acc[kt] = MFMA16(gf.lo, xf.hi, acc[kt]);
+                    const HiLo<bf16x8> xf = split8_trunc(xv);
+                    acc[kt] = mfma_32x32x16(gf.hi, xf.hi, acc[kt]);
+                    acc[kt] = mfma_32x32x16(gf.hi, xf.lo, acc[kt]);
+                    acc[kt] = mfma_32x32x16(gf.lo, xf.hi, acc[kt]);
                 }
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     colsum += st.g[u];
 #pragma unroll
-                    for (int kt = 0; kt < KT; ++kt) acc[kt] = MFMA(st.g[u], st.x[u][kt], acc[kt]);
+                    for (int kt = 0; kt < KT; ++kt) acc[kt] = mfma_32x32x2(st.g[u], st.x[u][kt], acc[kt]);
                 }
             }
         };

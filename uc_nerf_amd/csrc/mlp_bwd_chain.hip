@@ -19,16 +19,9 @@
 #include "common.h"
 #include "mlp_layout.h"
 #include "mlp_bwd_parts.h"
+#include "mfma_split.h"
 
 namespace ucnerf {
-
-typedef float c_f32x16 __attribute__((ext_vector_type(16)));
-typedef float c_f32x4 __attribute__((ext_vector_type(4)));
-typedef float c_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 c_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned c_u32x4 __attribute__((ext_vector_type(4)));
-#define CSB __builtin_amdgcn_sched_barrier(0)
-#define CMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 constexpr int BWD_HALF_STEPS = 128;            // VC 16 | FT 16 | BC 8 | L5 16 | L4 16 | L3 16 | L2 16 | L1 16 | BD 8
 constexpr int BWD_HALF_BYTES = 4096;           // [t 0..1][hi, lo][64 lanes][8 bf16]
@@ -43,9 +36,6 @@ struct BwdPackArgs {
     float* head;                   // [BWD_HEAD_FLOATS]
     long long p_crw, p_a1w, p_rw, p_aw, p_crb, p_a1b, p_rb, p_ab;
 };
-
-// feature held by element j of lane-half hh in k16-step q = (kt, s): accumulator register 8 s + j of row tile kt (as mlp_bf16.hip)
-__host__ __device__ inline int c_hid_feature16(int kt, int s, int j, int hh) { return 32 * kt + (j & 3) + 8 * (2 * s + (j >> 2)) + 4 * hh; }
 
 // Thread = one 16-byte fragment of the stream.  A[row][n] = W[n][col0 + row]: lane l supplies row 32 (2 pair + t) + (l & 31),
 // its eight elements the outputs n the B operand holds in that k16-step.
@@ -62,15 +52,15 @@ __global__ void __launch_bounds__(256) pack_bwd_kernel(BwdPackArgs a) {
         unsigned short v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const int n = c_hid_feature16(q >> 1, q & 1, e, lane >> 5);
+            const int n = hid_feature16(q >> 1, q & 1, e, lane >> 5);
             float w = 0.f;
             if (row < sc.rows) w = (sc.base_hi >= 0 && n >= 64) ? a.flat[sc.base_hi + (long long)(n - 64) * sc.ld + sc.col0 + row] : a.flat[sc.base + (long long)n * sc.ld + sc.col0 + row];
             const __bf16 hi = (__bf16)w;
             const __bf16 val = part ? (__bf16)(w - (float)hi) : hi;
             v[e] = __builtin_bit_cast(unsigned short, val);
         }
-        c_u32x4 o = {v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16), v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
-        reinterpret_cast<c_u32x4*>(a.out)[f] = o;
+        u32x4 o = {v[0] | ((unsigned)v[1] << 16), v[2] | ((unsigned)v[3] << 16), v[4] | ((unsigned)v[5] << 16), v[6] | ((unsigned)v[7] << 16)};
+        reinterpret_cast<u32x4*>(a.out)[f] = o;
     }
     if (f < BWD_HEAD_FLOATS) {
         float w = 0.f;
@@ -101,38 +91,14 @@ struct ChainArgs {
     float* g_base; float* g_adapt; float* g_sigma; // [m,4] each, 24-bit: (base rgb, base sigma), (adapt rgb, 0), (adapt sigma, 0, 0, 0)
 };
 
-__device__ __forceinline__ int c_opaque(int v) { asm volatile("" : "+v"(v)); return v; }
-// a result that is only needed at the end of the tile would be SUNK there, its operands kept alive (spilled) meanwhile: pin it where it is written
-__device__ __forceinline__ void c_pin(float& v) { asm volatile("" : "+v"(v)); }
-
-struct CFrag { c_bf16x8 hi, lo; };
-struct CAF { c_bf16x8 h0, l0, h1, l1; };
-
-// (hi, lo) split of eight values: hi = truncated bf16, lo = bf16_rne(x - hi) 
-// (the forward's split8, mlp_bf16.hip, rounds hi to nearest since round 5 -- the renders answer to an absolute 1e-4 bar; the gradients' bar is relative
-//  and they keep the truncated hi, which measured 0.2 % faster in the forward kernel)
-__device__ __forceinline__ CFrag c_split8(const float (&x)[8]) {
-    c_u32x4 hi;
-    CFrag f;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const unsigned b0 = __builtin_bit_cast(unsigned, x[j]), b1 = __builtin_bit_cast(unsigned, x[j + 1]);
-        hi[j >> 1] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        const c_f32x2 l = (c_f32x2){x[j], x[j + 1]} - (c_f32x2){__builtin_bit_cast(float, b0 & 0xffff0000u), __builtin_bit_cast(float, b1 & 0xffff0000u)};
-        f.lo[j] = (__bf16)l.x;
-        f.lo[j + 1] = (__bf16)l.y;
-    }
-    f.hi = __builtin_bit_cast(c_bf16x8, hi);
-    return f;
-}
-__device__ __forceinline__ void c_split_tile(const c_f32x16& x, CFrag& f0, CFrag& f1) {
+__device__ __forceinline__ void c_split_tile(const f32x16& x, HiLo<bf16x8>& f0, HiLo<bf16x8>& f1) {
     float t[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = x[e];
-    f0 = c_split8(t);
+    f0 = split8_trunc(t);
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = x[8 + e];
-    f1 = c_split8(t);
+    f1 = split8_trunc(t);
 }
 
 // ---- the weight ring: CHAIN_NB slots of one half-step (4 KB) each in LDS, shared by the block's four waves.  128 half-steps per tile
@@ -148,18 +114,14 @@ struct CPipe {
     unsigned dst;            // LDS byte address of this wave's quarter of slot 0
     const char* rd;          // this lane's 16 bytes of slot 0 (LDS)
 };
-// (issued from inline asm: the compiler treats a global_load_lds as an access to both memories and degrades every counted wait around it)
 __device__ __forceinline__ void c_dma(const CPipe& P, int hs_src, int slot) {
     const char* src = P.gsrc + (size_t)hs_src * BWD_HALF_BYTES;
     const unsigned dst = P.dst + slot * BWD_HALF_BYTES;
-    if (CHAIN_WAVES == 8) {                // eight waves: 512 bytes each -- the lower 32 lanes copy
-        if ((threadIdx.x & 32) == 0) asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
-    } else
-        asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory", "m0");
+    if (CHAIN_WAVES == 4 || (threadIdx.x & 32) == 0) lds_dma16(src, dst);      // (eight waves: 512 bytes each -- the lower 32 lanes copy)
 }
-__device__ __forceinline__ CAF c_ldaf(const CPipe& P, int slot) {
-    const c_bf16x8* a = reinterpret_cast<const c_bf16x8*>(P.rd + slot * BWD_HALF_BYTES);
-    CAF f;
+__device__ __forceinline__ PairFrags<bf16x8> c_ldaf(const CPipe& P, int slot) {
+    const bf16x8* a = reinterpret_cast<const bf16x8*>(P.rd + slot * BWD_HALF_BYTES);
+    PairFrags<bf16x8> f;
     f.h0 = a[0]; f.l0 = a[64]; f.h1 = a[128]; f.l1 = a[192];
     return f;
 }
@@ -172,9 +134,9 @@ __device__ __forceinline__ CAF c_ldaf(const CPipe& P, int slot) {
 // section behind them could start: 180 of the launch's 350 us (profiles/r03_experiments.md).
 // (hs: a constant once the caller's loops are unrolled)
 template <int YOUNGER>
-__device__ __forceinline__ CAF c_advance(const CPipe& P, int hs) {
+__device__ __forceinline__ PairFrags<bf16x8> c_advance(const CPipe& P, int hs) {
     static_assert(YOUNGER >= CHAIN_NB - 2 && YOUNGER <= 63, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(YOUNGER) : "memory");
+    wait_vmcnt_lgkmcnt<YOUNGER>();
     __builtin_amdgcn_s_barrier();
     c_dma(P, (hs + CHAIN_NB) % BWD_HALF_STEPS, hs % CHAIN_NB);
     return c_ldaf(P, (hs + 1) % CHAIN_NB);
@@ -195,8 +157,8 @@ __device__ __forceinline__ CRaw c_ld_tile(const float* set, size_t rb, int nt) {
     }
     return x;
 }
-__device__ __forceinline__ c_f32x16 c_unpack(const CRaw& r) {
-    c_f32x16 x;
+__device__ __forceinline__ f32x16 c_unpack(const CRaw& r) {
+    f32x16 x;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const P24Piece v = {{r.d[3 * q], r.d[3 * q + 1], r.d[3 * q + 2]}};
@@ -208,7 +170,7 @@ __device__ __forceinline__ c_f32x16 c_unpack(const CRaw& r) {
 }
 // (no predicate: the stores of a lane without a sample go to the spare row behind the set's last one -- `rb` then points there -- so that every
 //  wave issues the same number of vector-memory operations, which c_advance's counted waits rely on)
-__device__ __forceinline__ void c_st_tile(float* set, size_t rb, int nt, const c_f32x16& x) {
+__device__ __forceinline__ void c_st_tile(float* set, size_t rb, int nt, const f32x16& x) {
     char* row = reinterpret_cast<char*>(set) + rb;
 #pragma unroll
     for (int q = 0; q < 4; ++q) p24_store(row + P24_GROUP_BYTES * (8 * nt + 2 * q), p24_pack4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]));
@@ -218,24 +180,24 @@ __device__ __forceinline__ void c_st_tile(float* set, size_t rb, int nt, const c
 // has issued between the previous section and this one (see c_advance)
 constexpr int c_younger(int epi) { return CHAIN_NB - 2 + epi > 63 ? 63 : CHAIN_NB - 2 + epi; }
 template <int HS0, int PAIRS, int EPI>
-__device__ __forceinline__ void c_section(const CPipe& P, CAF& cur, const CFrag (&B)[8], c_f32x16 (&acc)[4]) {
+__device__ __forceinline__ void c_section(const CPipe& P, PairFrags<bf16x8>& cur, const HiLo<bf16x8> (&B)[8], f32x16 (&acc)[4]) {
 #pragma unroll
     for (int p = 0; p < PAIRS; ++p)
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            CSB;              // (one half-step at a time)
-            const CAF nxt = 8 * p + q < CHAIN_NB - 1 ? c_advance<c_younger(EPI)>(P, HS0 + 8 * p + q) : c_advance<CHAIN_NB - 2>(P, HS0 + 8 * p + q);
-            acc[2 * p] = CMFMA(cur.h0, B[q].hi, acc[2 * p]);
-            acc[2 * p] = CMFMA(cur.h0, B[q].lo, acc[2 * p]);
-            acc[2 * p] = CMFMA(cur.l0, B[q].hi, acc[2 * p]);
-            acc[2 * p + 1] = CMFMA(cur.h1, B[q].hi, acc[2 * p + 1]);
-            acc[2 * p + 1] = CMFMA(cur.h1, B[q].lo, acc[2 * p + 1]);
-            acc[2 * p + 1] = CMFMA(cur.l1, B[q].hi, acc[2 * p + 1]);
+            SB0;              // (one half-step at a time)
+            const PairFrags<bf16x8> nxt = 8 * p + q < CHAIN_NB - 1 ? c_advance<c_younger(EPI)>(P, HS0 + 8 * p + q) : c_advance<CHAIN_NB - 2>(P, HS0 + 8 * p + q);
+            acc[2 * p] = mfma_32x32x16(cur.h0, B[q].hi, acc[2 * p]);
+            acc[2 * p] = mfma_32x32x16(cur.h0, B[q].lo, acc[2 * p]);
+            acc[2 * p] = mfma_32x32x16(cur.l0, B[q].hi, acc[2 * p]);
+            acc[2 * p + 1] = mfma_32x32x16(cur.h1, B[q].hi, acc[2 * p + 1]);
+            acc[2 * p + 1] = mfma_32x32x16(cur.h1, B[q].lo, acc[2 * p + 1]);
+            acc[2 * p + 1] = mfma_32x32x16(cur.l1, B[q].hi, acc[2 * p + 1]);
             cur = nxt;
         }
 }
 
-__device__ __forceinline__ void c_zero(c_f32x16 (&acc)[4]) {
+__device__ __forceinline__ void c_zero(f32x16 (&acc)[4]) {
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -260,10 +222,10 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     char* const lds = reinterpret_cast<char*>(chain_lds);
     char* const park_bd = lds + CHAIN_PARK_OFF + wave * (CHAIN_PARK_BD + CHAIN_PARK_GBD) + lane * 12;          // piece (nt, q) of this lane at + (4 nt + q) * 64 * 12
-    c_f32x4* const park_gbd = reinterpret_cast<c_f32x4*>(lds + CHAIN_PARK_OFF + wave * (CHAIN_PARK_BD + CHAIN_PARK_GBD) + CHAIN_PARK_BD) + lane;
+    f32x4* const park_gbd = reinterpret_cast<f32x4*>(lds + CHAIN_PARK_OFF + wave * (CHAIN_PARK_BD + CHAIN_PARK_GBD) + CHAIN_PARK_BD) + lane;
     auto ld_bd = [&](int nt, size_t ro_ = 0) {
         if (CHAIN_WAVES != 4) return c_unpack(c_ld_tile(a.sv.bd, ro_, nt));       // (not parked: re-read, L2 resident)
-        c_f32x16 x;
+        f32x16 x;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const p24_u32x3 v = *reinterpret_cast<const p24_u32x3_a4*>(park_bd + (4 * nt + q) * 64 * 12);
@@ -281,11 +243,11 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
     };
     char* const park_g24 = lds + CHAIN_PARK_OFF + wave * (CHAIN_PARK_BD + CHAIN_PARK_GBD) + CHAIN_PARK_BD + lane * 12;      // (8 waves: g_bd as 24-bit pieces)
     auto ld_gbd = [&](int nt) {
-        c_f32x16 x;
+        f32x16 x;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (CHAIN_WAVES == 4) {
-                const c_f32x4 v = park_gbd[(nt * 4 + q) * 64];
+                const f32x4 v = park_gbd[(nt * 4 + q) * 64];
                 x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
             } else {
                 const p24_u32x3 v = *reinterpret_cast<const p24_u32x3_a4*>(park_g24 + (4 * nt + q) * 64 * 12);
@@ -297,10 +259,10 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         }
         return x;
     };
-    auto st_gbd = [&](int nt, const c_f32x16& x) {
+    auto st_gbd = [&](int nt, const f32x16& x) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (CHAIN_WAVES == 4) park_gbd[(nt * 4 + q) * 64] = (c_f32x4){x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+            if (CHAIN_WAVES == 4) park_gbd[(nt * 4 + q) * 64] = (f32x4){x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
             else {
                 const P24Piece pc = p24_pack4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
                 *reinterpret_cast<p24_u32x3_a4*>(park_g24 + (4 * nt + q) * 64 * 12) = (p24_u32x3){pc.d[0], pc.d[1], pc.d[2]};
@@ -316,12 +278,12 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
     P.gsrc = a.wstream + wave * SHARE + (lane & (SHARE / 16 - 1)) * 16;
     P.dst = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)(lds + CHAIN_RING_OFF) + wave * SHARE;
     P.rd = lds + CHAIN_RING_OFF + lane * 16;
-    auto launder = [&]() { unsigned o_ = (unsigned)(wave * SHARE + (lane & (SHARE / 16 - 1)) * 16); asm volatile("" : "+v"(o_)); P.gsrc = a.wstream + o_; };
+    auto launder = [&]() { P.gsrc = a.wstream + opaque((unsigned)(wave * SHARE + (lane & (SHARE / 16 - 1)) * 16)); };
 #pragma unroll
     for (int i = 0; i < CHAIN_NB; ++i) c_dma(P, i, i);        // half-steps 0 .. CHAIN_NB - 1 of the first tile
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CHAIN_NB - 1) : "memory");      // slot 0 has landed ...
-    __builtin_amdgcn_s_barrier();                                             // ... for every wave
-    CAF cur = c_ldaf(P, 0);
+    wait_vmcnt<CHAIN_NB - 1>();                     // slot 0 has landed ...
+    __builtin_amdgcn_s_barrier();                   // ... for every wave
+    PairFrags<bf16x8> cur = c_ldaf(P, 0);
 
     // Every wave of the block walks the same number of tiles (the ring is turned by all four together): a wave whose tile lies past the end
     // computes on the last sample's rows and stores nothing.
@@ -335,9 +297,9 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         const size_t ro_st = p24_offset((size_t)(valid ? s_raw : a.m), h, 32);      // ... for stores: sample m is the spare row of every set written here
 
         // ---- output stage (models.py:177-178 backwards)
-        const c_f32x4 raw = reinterpret_cast<const c_f32x4*>(a.raw)[s];
-        c_f32x4 gr = reinterpret_cast<const c_f32x4*>(a.g_raw)[s];
-        if (!valid) gr = (c_f32x4){0.f, 0.f, 0.f, 0.f};
+        const f32x4 raw = reinterpret_cast<const f32x4*>(a.raw)[s];
+        f32x4 gr = reinterpret_cast<const f32x4*>(a.g_raw)[s];
+        if (!valid) gr = (f32x4){0.f, 0.f, 0.f, 0.f};
         const float conf = a.feats_tiled ? a.feats[((size_t)(s >> 5) * a.F + a.F - 1) * 32 + (s & 31)] : a.feats[(size_t)s * a.ldf + a.F - 1];
         const float u = 1.f - conf, omu = 1.f - u;
         const float gp[4] = {gr.x * raw.x * (1.f - raw.x), gr.y * raw.y * (1.f - raw.y), gr.z * raw.z * (1.f - raw.z), raw.w > 0.f ? gr.w : 0.f};
@@ -350,9 +312,9 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
             p24_store(reinterpret_cast<char*>(a.g_sigma) + r12, p24_pack4(ga4[3], 0.f, 0.f, 0.f));             // adapt sigma
         }
 
-        c_f32x16 acc[4];
+        f32x16 acc[4];
         CRaw hn[4], hm[4], hx[4], bcr[4], bdr[4];
-        CFrag X[8];
+        HiLo<bf16x8> X[8];
         float ad[4] = {0.f, 0.f, 0.f, 0.f}, bs[4] = {0.f, 0.f, 0.f, 0.f};      // this lane's share of the adapt / base head outputs
 
         // ---- adapt heads backwards + relu of [views | view_confi]: g_vc
@@ -360,13 +322,13 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         for (int nt = 0; nt < 4; ++nt) hn[nt] = c_ld_tile(a.sv.vc, ro, nt);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            const c_f32x16 hv_ = c_unpack(hn[nt]);
+            const f32x16 hv_ = c_unpack(hn[nt]);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int f0 = 32 * nt + 8 * q + 4 * c_opaque(h);       // (laundered: the table never changes, so its reads would be hoisted out of the tile loop and spilled)
-                c_f32x4 w[4];
+                const int f0 = 32 * nt + 8 * q + 4 * opaque(h);       // (laundered: the table never changes, so its reads would be hoisted out of the tile loop and spilled)
+                f32x4 w[4];
 #pragma unroll
-                for (int o = 0; o < 4; ++o) w[o] = *reinterpret_cast<const c_f32x4*>(&hw[(4 + o) * 128 + f0]);
+                for (int o = 0; o < 4; ++o) w[o] = *reinterpret_cast<const f32x4*>(&hw[(4 + o) * 128 + f0]);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float v = hv_[4 * q + c];
@@ -375,12 +337,12 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
 #pragma unroll
                     for (int o = 0; o < 4; ++o) ad[o] += v * w[o][c];
                 }
-                c_pin(ad[0]); c_pin(ad[1]); c_pin(ad[2]); c_pin(ad[3]);
-                CSB;                                         // (a fence per group: the scheduler otherwise reads every head weight of the tile up front and spills them)
+                pin(ad[0]); pin(ad[1]); pin(ad[2]); pin(ad[3]);
+                SB0;                                         // (a fence per group: the scheduler otherwise reads every head weight of the tile up front and spills them)
             }
             c_st_tile(a.G_vc, ro_st, nt, acc[nt]);
             c_split_tile(acc[nt], X[2 * nt], X[2 * nt + 1]);
-            CSB;
+            SB0;
         }
 
         // ---- [views | view_confi]^T: g_f (f = feature_linear's output, no activation)
@@ -390,7 +352,7 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         for (int nt = 0; nt < 4; ++nt) {
             c_st_tile(a.G_f, ro_st, nt, acc[nt]);
             c_split_tile(acc[nt], X[2 * nt], X[2 * nt + 1]);
-            CSB;
+            SB0;
         }
 
         // ---- feature_linear^T: g_gx
@@ -401,7 +363,7 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
 
         // ---- confidence-bias net^T first (its operand g_bc = g_gx * h5 dies before the trunk's state is born): gradient of the image
         //      features, columns n_mvs .. n_mvs + n_img of g_feats
-        auto small_out = [&](const c_f32x16 (&r2)[4], int col0, int rows) {
+        auto small_out = [&](const f32x16 (&r2)[4], int col0, int rows) {
             if (valid) {
                 float* dst = a.g_feats + (size_t)s * a.ldgf + col0;
 #pragma unroll
@@ -417,40 +379,40 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
             }
         };
         {
-            CFrag Z[8];
+            HiLo<bf16x8> Z[8];
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                c_f32x16 gbc;
-                const c_f32x16 h5_ = c_unpack(hn[nt]);
+                f32x16 gbc;
+                const f32x16 h5_ = c_unpack(hn[nt]);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) gbc[r] = acc[nt][r] * h5_[r];
                 c_st_tile(a.G_bc, ro_st, nt, gbc);
                 c_split_tile(gbc, Z[2 * nt], Z[2 * nt + 1]);
-                CSB;
+                SB0;
             }
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) hm[nt] = c_ld_tile(a.sv.h[4], ro, nt);      // for the first trunk epilogue, two sections away
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) { bcr[nt] = c_ld_tile(a.sv.bc, ro, nt); bdr[nt] = c_ld_tile(a.sv.bd, ro, nt); }      // for the epilogue behind this section
-            c_f32x16 a2[4];
+            f32x16 a2[4];
             c_zero(a2);
             launder(); c_section<32, 1, 64>(P, cur, Z, a2)               /* G_bc stores, h4, b_c and b_d loads */;
             small_out(a2, a.n_mvs, a.n_img);
         }
-        CSB;
+        SB0;
 
         // ---- gx = h5 * bc (feature_linear's input), g_h5 = g_gx * bc + base heads^T g_base, relu / b_d backward of layer 5
         {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                const c_f32x16 bct = c_unpack(bcr[nt]), bdt = c_unpack(bdr[nt]), h5_ = c_unpack(hn[nt]);
-                c_f32x16 gxv, gy, gb;
+                const f32x16 bct = c_unpack(bcr[nt]), bdt = c_unpack(bdr[nt]), h5_ = c_unpack(hn[nt]);
+                f32x16 gxv, gy, gb;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int f0 = 32 * nt + 8 * q + 4 * c_opaque(h);       // (laundered: the table never changes, so its reads would be hoisted out of the tile loop and spilled)
-                    c_f32x4 w[4];
+                    const int f0 = 32 * nt + 8 * q + 4 * opaque(h);       // (laundered: the table never changes, so its reads would be hoisted out of the tile loop and spilled)
+                    f32x4 w[4];
 #pragma unroll
-                    for (int o = 0; o < 4; ++o) w[o] = *reinterpret_cast<const c_f32x4*>(&hw[o * 128 + f0]);
+                    for (int o = 0; o < 4; ++o) w[o] = *reinterpret_cast<const f32x4*>(&hw[o * 128 + f0]);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const int r = 4 * q + c;
@@ -463,15 +425,15 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
                         gb[r] = gpre * hv;
                         gy[r] = gpre * bdt[r];
                     }
-                    c_pin(bs[0]); c_pin(bs[1]); c_pin(bs[2]); c_pin(bs[3]);
-                    CSB;
+                    pin(bs[0]); pin(bs[1]); pin(bs[2]); pin(bs[3]);
+                    SB0;
                 }
                 st_bd(nt, bdr[nt]);
                 st_gbd(nt, gb);
                 c_st_tile(a.gx, ro_st, nt, gxv);
                 c_st_tile(a.G_y[5], ro_st, nt, gy);
                 c_split_tile(gy, X[2 * nt], X[2 * nt + 1]);
-                CSB;
+                SB0;
             }
         }
 
@@ -479,9 +441,9 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         auto trunk_epi = [&](float* G_out, const CRaw (&hraw)[4]) {
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                const c_f32x16 hcur_ = c_unpack(hraw[nt]);
-                const c_f32x16 bdt = ld_bd(nt, ro);
-                c_f32x16 gb = ld_gbd(nt), gy;
+                const f32x16 hcur_ = c_unpack(hraw[nt]);
+                const f32x16 bdt = ld_bd(nt, ro);
+                f32x16 gb = ld_gbd(nt), gy;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float hv = hcur_[r];
@@ -492,7 +454,7 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
                 st_gbd(nt, gb);
                 c_st_tile(G_out, ro_st, nt, gy);
                 c_split_tile(gy, X[2 * nt], X[2 * nt + 1]);
-                CSB;
+                SB0;
             }
         };
         // The activation set a layer's epilogue needs is requested TWO layers early, into one of three register sets (hx takes the registers b_c and
@@ -509,7 +471,7 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
                 _Pragma("unroll")                                                                         \
                 for (int nt = 0; nt < 4; ++nt) NXT[nt] = c_ld_tile(a.sv.h[(L) - 3], ro, nt);             \
             }                                                                                             \
-            CSB;                                                                                          \
+            SB0;                                                                                          \
             trunk_epi(a.G_y[(L) - 1], CUR);                                                               \
         }
         UCNERF_CHAIN_LAYER(40, 5, hm, hn, 48)   // uses h4 (requested before the confidence-bias net's section), requests h2; in front: gx, G_y[5] stores, h3 loads
@@ -522,16 +484,16 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         // ---- depth-bias net: g_bd = sum_l g_pre_l * y_l with y_l = h_l / b_d on the active units; then its transposed layer
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            const c_f32x16 bdt = ld_bd(nt, ro), gb = ld_gbd(nt);
-            c_f32x16 g;
+            const f32x16 bdt = ld_bd(nt, ro), gb = ld_gbd(nt);
+            f32x16 g;
 #pragma unroll
             for (int r = 0; r < 16; ++r) g[r] = gb[r] != 0.f ? gb[r] / bdt[r] : 0.f;
             c_st_tile(a.G_bd, ro_st, nt, g);
             c_split_tile(g, X[2 * nt], X[2 * nt + 1]);
-            CSB;
+            SB0;
         }
         {
-            c_f32x16 a2[4];
+            f32x16 a2[4];
             c_zero(a2);
             launder(); c_section<120, 1, 32>(P, cur, X, a2)              /* G_y[0] and G_bd stores */;
             small_out(a2, 0, a.n_mvs);
@@ -542,14 +504,14 @@ __global__ void __launch_bounds__(64 * CHAIN_WAVES, CHAIN_WAVES / 4) mlp_bwd_cha
         for (int o = 0; o < 4; ++o) {
             ad[o] += __shfl_xor(ad[o], 32);
             bs[o] += __shfl_xor(bs[o], 32);
-            ad[o] += hw[c_opaque(1024 + 4 + o)];
-            bs[o] += hw[c_opaque(1024 + o)];
+            ad[o] += hw[opaque(1024 + 4 + o)];
+            bs[o] += hw[opaque(1024 + o)];
         }
         const float gu = gp[0] * (ad[0] - bs[0]) + gp[1] * (ad[1] - bs[1]) + gp[2] * (ad[2] - bs[2]) + gp[3] * (bs[3] - ad[3]);
         if (h == 0 && valid) a.g_feats[(size_t)s * a.ldgf + a.F - 1] = -gu;
 
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the copies still in flight land before the block gives its LDS back
+    wait_vmcnt<0>();          // the copies still in flight land before the block gives its LDS back
 }
 
 // ---- host side

@@ -32,6 +32,10 @@ enum { SEC_BD = 0, SEC_L0 = 1, SEC_BC = 7, SEC_FT = 8, SEC_VC = 9 };
 
 // feature index held by accumulator register r (0..15) of row-tile kt on lane-half h
 __host__ __device__ inline int acc_feature(int kt, int r, int h) { return 32 * kt + (r & 3) + 8 * (r >> 2) + 4 * h; }
+// The split-bf16 kernels (mlp_bf16.hip forward, mlp_bwd_chain.hip backward) feed a hidden layer's accumulators to the next layer as k16-steps:
+// feature held by element j of lane-half hh in hidden k16-step q = (kt, s) = accumulator register 8 s + j of row-tile kt.  Both packers,
+// build_pack_index_bf16 and pack_bwd_kernel, order the weights by it.
+__host__ __device__ inline int hid_feature16(int kt, int s, int j, int hh) { return 32 * kt + (j & 3) + 8 * (2 * s + (j >> 2)) + 4 * hh; }
 
 // Stream = [k-steps of all sections in execution order][wrap: copy of the first RING k-steps][constants].
 //   execution order: bd | L0 | L1..L4 | L5 (pe part, hidden part) | bc | ft | vc (hidden part, dir part)

@@ -28,36 +28,15 @@
 #include "common.h"
 #include "mlp_layout.h"
 #include "mlp_bwd_parts.h"
+#include "mfma_split.h"
 
 namespace ucnerf {
 
-typedef float w_f32x16 __attribute__((ext_vector_type(16)));
-typedef float w_f32x4 __attribute__((ext_vector_type(4)));
-typedef float w_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 w_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned w_u32x4 __attribute__((ext_vector_type(4)));
-typedef w_u32x4 w_u32x4_a4 __attribute__((aligned(4)));
-#define WMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 
 constexpr int WG_STAGE = 64;              // samples per stage (four k16-steps)
 constexpr int WG_KS = WG_STAGE / 16;
 constexpr int WG_THREADS = 768;            // waves 0-3 produce the X operand, 4-7 the G operand, 8-11 multiply
-
-struct WFrag { w_bf16x8 hi, lo; };
-__device__ __forceinline__ WFrag w_split8(const float (&x)[8]) {
-    w_u32x4 hi;
-    WFrag f;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) {
-        const unsigned b0 = __builtin_bit_cast(unsigned, x[j]), b1 = __builtin_bit_cast(unsigned, x[j + 1]);
-        hi[j >> 1] = __builtin_amdgcn_perm(b1, b0, 0x07060302u);
-        const w_f32x2 l = (w_f32x2){x[j], x[j + 1]} - (w_f32x2){__builtin_bit_cast(float, b0 & 0xffff0000u), __builtin_bit_cast(float, b1 & 0xffff0000u)};
-        f.lo[j] = (__bf16)l.x;
-        f.lo[j + 1] = (__bf16)l.y;
-    }
-    f.hi = __builtin_bit_cast(w_bf16x8, hi);
-    return f;
-}
 
 // LDS image of one stage and operand: [k16-step][hi, lo][row tile 0..3][64 lanes][8 bf16] = 32 KB: the fragment of (k-step, tile) of
 // lane (feature i, half hh) = samples 16 ks + 8 hh + 0..7 of feature 32 tile + i, ready for one ds_read_b128 per plane
@@ -82,7 +61,6 @@ __device__ __forceinline__ void wg_atomic_add(float* p, float v) {
     typedef float __attribute__((address_space(1))) * gp_t;
     __hip_atomic_fetch_add((gp_t)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }     // LDS traffic only: loads in flight stay in flight
 
 #define WG_T(k)
 #define WG_STAMP_ARG
@@ -93,7 +71,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
     const bool producer = wave < 8;                           // (wave-uniform)
     const int t8 = tid & 255;
     int m_ = a.m, stages_ = a.stages;                        // (made opaque: the compiler otherwise re-reads kernel arguments wherever it is short of a register)
-    asm volatile("" : "+s"(m_), "+s"(stages_));
+    asm volatile("" : "+s"(m_), "+s"(stages_));              // (one statement: two sopaque() calls allocate the scalar registers differently)
     const int wg_m = m_, wg_stages = stages_;
     const int grp = t8 & 31, oct = t8 >> 5;                   // rows:  columns 4 grp .. 4 grp + 3, samples 8 oct .. 8 oct + 7 of the stage
     const int tcol = t8 & 127, ttile = t8 >> 7;               // tiles: column tcol, samples 32 ttile .. 32 ttile + 31 of the stage
@@ -233,9 +211,9 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
     auto total_even = [&]() { return (__builtin_amdgcn_readfirstlane(lds_total) + 1) & ~1; };
 
     if (producer) {
-        struct Regs { w_u32x4 d[8]; };
+        struct Regs { u32x4 d[8]; };
         // global -> registers, and nothing else: rows / columns outside the matrix read a clamped (valid) piece that `convert` replaces by zero
-        auto fetch_side = [&](auto XS, w_u32x4 (&d)[8], const WgPair& q, int stg) {
+        auto fetch_side = [&](auto XS, u32x4 (&d)[8], const WgPair& q, int stg) {
             constexpr bool xs = decltype(XS)::value;
             const int mode = xs ? q.xmode : WG_X24;
             // (the descriptor came through LDS: the compiler no longer knows that its pointers are global memory, and a FLAT load counts as an LDS
@@ -270,20 +248,20 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                d[e] = *(const w_u32x4_a4 __attribute__((address_space(1)))*)(base + off[e]);
+                d[e] = *(const u32x4_a4 __attribute__((address_space(1)))*)(base + off[e]);
             }
         };
-        w_f32x2 colsum[2] = {{0.f, 0.f}, {0.f, 0.f}};        // bias gradients of columns 4 grp .. 4 grp + 3: this thread's samples
+        f32x2 colsum[2] = {{0.f, 0.f}, {0.f, 0.f}};        // bias gradients of columns 4 grp .. 4 grp + 3: this thread's samples
         // registers -> (hi, lo) fragments -> LDS: every value is split exactly once
         auto put_frag = [&](char* Ol, const float (&x)[8], int f, int o) {
-            const WFrag fr = w_split8(x);
+            const HiLo<bf16x8> fr = split8_trunc(x);
             const int off = frag_off(f, o);
-            *reinterpret_cast<w_bf16x8*>(Ol + off) = fr.hi;
-            *reinterpret_cast<w_bf16x8*>(Ol + off + 4 * 64 * 16) = fr.lo;
+            *reinterpret_cast<bf16x8*>(Ol + off) = fr.hi;
+            *reinterpret_cast<bf16x8*>(Ol + off + 4 * 64 * 16) = fr.lo;
         };
         // rows (24-bit or fp32 pieces): fragment c = column 4 grp + c of the thread's eight rows.  CLEAN (uniform: a whole stage of a 128-wide operand)
         // = nothing to zero; otherwise clamped rows / columns are zeroed with one AND per value (a mask per column times a mask per row)
-        auto convert_rows = [&](auto XS, auto IS24, auto CLEAN, const w_u32x4 (&d)[8], int width, int stg, char* Ol, bool live) {
+        auto convert_rows = [&](auto XS, auto IS24, auto CLEAN, const u32x4 (&d)[8], int width, int stg, char* Ol, bool live) {
             constexpr bool xs = decltype(XS)::value, is24 = decltype(IS24)::value, clean = decltype(CLEAN)::value;
             const int s0 = stg * WG_STAGE + 8 * oct;
             unsigned cm[4], rm[8];
@@ -306,7 +284,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
                     }
                 if (!xs) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) colsum[cp >> 1] += (w_f32x2){x[0][e], x[1][e]};
+                    for (int e = 0; e < 8; ++e) colsum[cp >> 1] += (f32x2){x[0][e], x[1][e]};
                 }
                 put_frag(Ol, x[0], 4 * grp + cp, oct);
                 put_frag(Ol, x[1], 4 * grp + cp + 1, oct);
@@ -318,7 +296,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
                 for (int e = 0; e < 8; ++e) asm volatile("" ::"v"(d[e][3]));
             }
         };
-        auto convert_side = [&](auto XS, const w_u32x4 (&d)[8], const WgPair& q, int stg, char* Ol, bool live) {
+        auto convert_side = [&](auto XS, const u32x4 (&d)[8], const WgPair& q, int stg, char* Ol, bool live) {
             constexpr bool xs = decltype(XS)::value;
             const int mode = xs ? q.xmode : WG_X24;
             const int width = xs ? q.w : q.nout;
@@ -359,7 +337,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
                     }
                 }
             }
-            colsum[0] = colsum[1] = (w_f32x2){0.f, 0.f};
+            colsum[0] = colsum[1] = (f32x2){0.f, 0.f};
         };
         WgCur fc, cv;                                         // the stage fetched next, the stage converted next
         WgPair fq, cq;                                        // ... and their pairs
@@ -387,8 +365,8 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
             convert(A, 0);
             WG_T(0)
             for (int k = 0; k < k_max && k < total_even(); k += WG_UNROLL) {
-                fetch(A); wg_barrier(); convert(B, 1);
-                fetch(B); wg_barrier(); convert(A, 0);
+                fetch(A); lds_barrier(); convert(B, 1);
+                fetch(B); lds_barrier(); convert(A, 0);
             }
         };
         // (the X producers are the block's first four waves: their stage is the longer one -- fetch + conversion 4.5 k cycles against the G side's
@@ -400,7 +378,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
 
     // ---- consumers: wave 8 + nt owns output rows 32 nt .. 32 nt + 31, all four column tiles
     const int nt = wave - 8;
-    w_f32x16 acc[4];
+    f32x16 acc[4];
     auto zero = [&]() {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -414,16 +392,16 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
         const char* const Xl = Gl + WG_OP_BYTES;
 #pragma unroll
         for (int ks = 0; ks < WG_KS; ++ks) {
-            const w_bf16x8* ga = reinterpret_cast<const w_bf16x8*>(Gl) + (ks * 2 * 4 + nt) * 64 + (lane & 32) + swz(nt, lane >> 5, lane & 31);
-            const w_bf16x8 ahi = ga[0], alo = ga[4 * 64];
+            const bf16x8* ga = reinterpret_cast<const bf16x8*>(Gl) + (ks * 2 * 4 + nt) * 64 + (lane & 32) + swz(nt, lane >> 5, lane & 31);
+            const bf16x8 ahi = ga[0], alo = ga[4 * 64];
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt) {
                 if (full || 32 * kt < q.w) {
-                    const w_bf16x8* xb = reinterpret_cast<const w_bf16x8*>(Xl) + (ks * 2 * 4 + kt) * 64 + (lane & 32) + swz(kt, lane >> 5, lane & 31);
-                    const w_bf16x8 bhi = xb[0], blo = xb[4 * 64];
-                    acc[kt] = WMFMA(ahi, bhi, acc[kt]);
-                    acc[kt] = WMFMA(ahi, blo, acc[kt]);
-                    acc[kt] = WMFMA(alo, bhi, acc[kt]);
+                    const bf16x8* xb = reinterpret_cast<const bf16x8*>(Xl) + (ks * 2 * 4 + kt) * 64 + (lane & 32) + swz(kt, lane >> 5, lane & 31);
+                    const bf16x8 bhi = xb[0], blo = xb[4 * 64];
+                    acc[kt] = mfma_32x32x16(ahi, bhi, acc[kt]);
+                    acc[kt] = mfma_32x32x16(ahi, blo, acc[kt]);
+                    acc[kt] = mfma_32x32x16(alo, bhi, acc[kt]);
                 }
             }
         }
@@ -477,7 +455,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
         for (int h = 0; h < WG_UNROLL; ++h) {
             if (wave == 8) while (!g_end && g_next < mu.j + 1 + WG_LEAD) grab();      // (before the barrier: visible to every wave from this stage index on)
             WG_T(0)
-            wg_barrier();                                    // image h holds stage k + h; everyone is done with the other one
+            lds_barrier();                                    // image h holds stage k + h; everyone is done with the other one
             WG_T(1)
             if (mu.left > 0) {
                 multiply(mq, h);
