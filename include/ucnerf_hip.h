@@ -322,8 +322,11 @@ typedef struct {
                              0: bf16 (8 significant bits per term; any float32 range).  The default.
                              1: fp16 (v_mfma_f32_32x32x16_f16: 11 significant bits per term at the same matrix-core rate, so the three-product
                                 split holds ~22 bits -- rendered outputs at float32 level where the bf16 split is at 16 .. 17 bits).  fp16's RANGE
-                                is the price: the conversions round toward zero, so an activation beyond 131 008 is clamped -- finite, but wrong
-                                (float32 itself resolves no more than 1e-2 of it) -- and a term below 6e-5 is held with an absolute resolution of 3e-8.  Inference forward
+                                is the price.  ACTIVATIONS are converted toward zero, so one beyond 131 008 is clamped -- finite, but wrong
+                                (float32 itself resolves no more than 1e-2 of it) -- and never becomes an infinity.  That holds for the activation
+                                side ONLY: a WEIGHT beyond 65 504 is packed as hi = inf, lo = -inf and its products are NaN (the packers round to
+                                nearest and do not clamp).  A term below 6e-5 is held with an absolute resolution of 3e-8.  None of this is reported
+                                by these calls; the guarded calls below (ucnerf_*_guarded) detect the overflow side on the device.  Inference forward
                                 only (ucnerf_mlp_fwd_train refuses it).  Ignored by precision 0. */
 } ucnerf_mlp_config;
 
@@ -365,6 +368,34 @@ typedef struct {
     float* raw;                /* [m,4] out: rgb (after sigmoid), sigma (after relu) */
 } ucnerf_mlp_params;
 int ucnerf_mlp_fwd(const ucnerf_mlp_params* p, void* stream);
+
+/* The guarded fp16 split (additive to ABI v6: no struct changes; the guard is a property of the CALL, cfg.operand stays 0 / 1).
+ *
+ * `status` / `run_if` is one 4-byte-aligned 32-bit word in DEVICE memory, owned, zeroed and kept alive by the caller.  The library only ever ORs
+ * bits into it (vector-memory atomics) -- it is sticky until the caller clears it:
+ *     bit 0: a guarded forward formed an fp16 hi term of magnitude 65 504 from an activation or input (any |x| >= 65 504, infinities and NaNs
+ *            included).  Conservative: values are only clamped from 131 008 on; flagging early costs a replay, never a wrong result.
+ *     bit 1: a guarded pack met a weight whose fp16 hi term is not finite or reaches 65 504.
+ * What is NOT detected: terms below 6e-5 (fp16's subnormal side) lose relative precision exactly as with the unguarded fp16 terms; they stay within
+ * the absolute parity bar and raise no flag.
+ *
+ * ucnerf_*_guarded: the call of the same name on fp16 terms (cfg.operand must be 1, precision 1 .. 3) with range detection; same outputs, bit for bit,
+ *     as the unguarded call.  Nothing is written to `status` when nothing left the range.
+ * ucnerf_*_if: the call of the same name (any operand; in practice 0, bf16 terms) whose MLP / pack kernels first read *run_if and do nothing when it
+ *     is zero: enqueued directly behind the guarded call of the same pass, with run_if = status and a bf16-term stream, it re-renders the pass on
+ *     bf16 terms exactly when something saturated -- no host synchronisation.  The result is then bit-identical to the plain bf16-term call, else
+ *     to the plain fp16-term call.  ucnerf_render_fused_fwd_if repeats the whole pass from the same inputs: its launches around the MLP (direction
+ *     features, gather, compositing, re-sampling) are not conditional and rewrite the values already there when the MLP launch was skipped; it
+ *     records no events.
+ * A null word is UCNERF_EINVAL, like a negative count.  Inference forward only. */
+int ucnerf_mlp_fwd_guarded(const ucnerf_mlp_params* p, uint32_t* status, void* stream);
+int ucnerf_mlp_fwd_if(const ucnerf_mlp_params* p, const uint32_t* run_if, void* stream);
+int ucnerf_mlp_pack_guarded(const ucnerf_mlp_config* cfg, const float* flat_params, const int32_t* idx, float* stream_out, uint32_t* status, void* stream);
+int ucnerf_mlp_pack_if(const ucnerf_mlp_config* cfg, const float* flat_params, const int32_t* idx, float* stream_out, const uint32_t* run_if, void* stream);
+int ucnerf_mlp_pack_tensors_guarded(const ucnerf_mlp_config* cfg, int32_t n_tensors, const void* const* tensor_ptrs_host, const int64_t* tensor_numel_host,
+                                    const int32_t* idx, float* stream_out, uint32_t* status, void* stream);
+int ucnerf_mlp_pack_tensors_if(const ucnerf_mlp_config* cfg, int32_t n_tensors, const void* const* tensor_ptrs_host, const int64_t* tensor_numel_host,
+                               const int32_t* idx, float* stream_out, const uint32_t* run_if, void* stream);
 
 /* Backward (autograd of network/models.py:138-184): re-runs the forward keeping the per-layer activations (unless
  * saved_valid), then walks the layers backwards (bwd_mode).  Produces d(feats) and ACCUMULATES the parameter gradients
@@ -619,6 +650,9 @@ typedef struct {
 } ucnerf_render_params;
 int64_t ucnerf_render_workspace_floats(int32_t n, int32_t S, int32_t V);
 int ucnerf_render_fused_fwd(const ucnerf_render_params* p, void* stream);
+/* The guarded fp16 split of a whole pass (see ucnerf_mlp_fwd_guarded): same parameters, plus the status / condition word. */
+int ucnerf_render_fused_fwd_guarded(const ucnerf_render_params* p, uint32_t* status, void* stream);
+int ucnerf_render_fused_fwd_if(const ucnerf_render_params* p, const uint32_t* run_if, void* stream);
 /* Channel-last repack of the gather sources named in `p` (vol[3] -> [D,h,w,8] each, img_feat -> [V,H,W,8], imgs -> [V,H,W,4] = (r,g,b,0); fp32, or
  * bf16 when p->cl.bf16) into `dst` (ucnerf_gather_repack_floats(p) floats, 16-byte aligned), and the pointers of the result into `out` (rgb_stride 4,
  * bf16 as asked).  PER SOURCE: an entry of p->cl that is already set -- a source handed over in place -- is kept as it is (copied to `out`, nothing

@@ -40,9 +40,23 @@ def set_training_precision(precision):
 
 def set_split_operand(kind):
     """The 16-bit terms of the split precisions: "bf16" (default: 8 significant bits per term, float32's range) or "fp16" (11 bits per term at the
-    same matrix-core rate: renders at float32 level, no measurable kernel time (+0.1 %); fp16's range -- an activation beyond 65 504 overflows) -- ops.set_split_operand."""
+    same matrix-core rate: renders at float32 level, no measurable kernel time (+0.1 %); fp16's range -- an activation beyond 65 504 overflows) or
+    "fp16_guarded" (the fp16 terms with a range check on the device: a launch in which an activation or a weight reached 65 504 is re-rendered on
+    bf16 terms without a host synchronisation; the status word is sticky until split_guard_clear()) -- ops.set_split_operand."""
     from . import ops
     ops.set_split_operand(kind)
+
+
+def split_guard_status(clear=False):
+    """The "fp16_guarded" status word of the current device (bit 0: an activation saturated, bit 1: a weight); synchronises -- ops.split_guard_status."""
+    from . import ops
+    return ops.split_guard_status(clear)
+
+
+def split_guard_clear():
+    """Enqueues a clear of the "fp16_guarded" status word on the current stream -- ops.split_guard_clear."""
+    from . import ops
+    ops.split_guard_clear()
 
 
 def set_backward_mode(mode):
@@ -58,7 +72,7 @@ def install_dropin(precision=None, training_precision=None, split_operand=None):
     train.py imports resolve here unchanged.  See INTEGRATION.md.
     precision: MLP arithmetic of `rendering()` under torch.no_grad() (None keeps the default, "bf16x3_fused"; "f32" = exact fp32 MFMA);
     training_precision: of the training forward (None keeps "f32");
-    split_operand: the 16-bit terms of the split precisions under no_grad, "bf16" or "fp16" (None keeps the current setting: "bf16" unless
+    split_operand: the 16-bit terms of the split precisions under no_grad, "bf16", "fp16" or "fp16_guarded" (None keeps the current setting: "bf16" unless
     UCNERF_SPLIT_OPERAND says otherwise) -- set_split_operand."""
     import importlib
     if precision is not None:

@@ -205,6 +205,15 @@ SYMBOLS = {
     "ucnerf_mlp_pack_tensors": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "ucnerf_mlp_unpack_grad": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "ucnerf_mlp_fwd": (C.c_int, [_P, _P]),
+    # the guarded fp16 split (additive to ABI v6): the call of the same name plus a status / condition word
+    "ucnerf_mlp_fwd_guarded": (C.c_int, [_P, _P, _P]),
+    "ucnerf_mlp_fwd_if": (C.c_int, [_P, _P, _P]),
+    "ucnerf_mlp_pack_guarded": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ucnerf_mlp_pack_if": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ucnerf_mlp_pack_tensors_guarded": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "ucnerf_mlp_pack_tensors_if": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "ucnerf_render_fused_fwd_guarded": (C.c_int, [_P, _P, _P]),
+    "ucnerf_render_fused_fwd_if": (C.c_int, [_P, _P, _P]),
     "ucnerf_mlp_bwd_workspace_floats": (C.c_int64, [_P, C.c_int32]),
     "ucnerf_mlp_bwd": (C.c_int, [_P, _P]),
     "ucnerf_mlp_fwd_train": (C.c_int, [_P, _P, C.c_int32, _P]),

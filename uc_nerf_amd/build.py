@@ -19,7 +19,11 @@ VARIANTS = [("mlp_bf16.hip", "mlp_bf16_plain.o", ["-DUCNERF_BF16_BUILD_TERMS=1"]
             # the same three builds with fp16 terms (ucnerf_mlp_config.operand == 1, ABI v6): entry points under the suffix _h16
             ("mlp_bf16.hip", "mlp_h16.o", ["-DUCNERF_OPERAND_FP16=1"]),
             ("mlp_bf16.hip", "mlp_h16_plain.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_BF16_BUILD_TERMS=1"]),
-            ("mlp_bf16.hip", "mlp_h16_tail.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_BF16_BUILD_TAIL=1"])]
+            ("mlp_bf16.hip", "mlp_h16_tail.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_BF16_BUILD_TAIL=1"]),
+            # ... and the fp16-term builds once more with range detection compiled in (the guarded split, ucnerf_*_guarded): suffix _g16
+            ("mlp_bf16.hip", "mlp_g16.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1"]),
+            ("mlp_bf16.hip", "mlp_g16_plain.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1", "-DUCNERF_BF16_BUILD_TERMS=1"]),
+            ("mlp_bf16.hip", "mlp_g16_tail.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1", "-DUCNERF_BF16_BUILD_TAIL=1"])]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mlp_layout.h"), os.path.join(CSRC, "sincos_cw.h"), os.path.join(CSRC, "gather_cl_device.h"), os.path.join(CSRC, "mlp_bwd_parts.h"), os.path.join(CSRC, "p24.h"), os.path.join(CSRC, "composite_device.h"), os.path.join(CSRC, "sample_pdf_device.h"), os.path.join(CSRC, "raygen_device.h"), os.path.join(CSRC, "mfma_split.h"),
            os.path.join(HERE, "..", "include", "ucnerf_hip.h")]
 # -ffp-contract=off: the sample_pdf / sampling kernels reproduce torch-CPU roundings (separate mul and add)

@@ -40,6 +40,19 @@ struct Mat33 { float m[9]; };
 
 int device_cus();   // of the CURRENT device, cached per device (thread-safe)
 
+// The status / condition word of the guarded split (ucnerf_*_guarded, ucnerf_*_if): a property of the CALL, not of ucnerf_mlp_config, so it
+// travels beside the parameter structs -- the entry point sets it for the calling thread (SplitGuardScope), the launchers of mlp_bf16.hip read it.
+//   GUARD_DETECT: fp16 terms with range detection, `word` = the status word the kernels OR into;
+//   GUARD_RUN_IF: `word` = the condition word; a kernel whose word reads zero does nothing.
+enum { GUARD_NONE = 0, GUARD_DETECT = 1, GUARD_RUN_IF = 2 };
+struct SplitGuard { int mode; unsigned* word; };
+SplitGuard& split_guard();   // thread-local (mlp.hip); {GUARD_NONE, nullptr} outside a guarded entry point
+struct SplitGuardScope {
+    SplitGuard saved;
+    SplitGuardScope(int mode, void* word) : saved(split_guard()) { split_guard() = SplitGuard{mode, static_cast<unsigned*>(word)}; }
+    ~SplitGuardScope() { split_guard() = saved; }
+};
+
 // ucnerf_build_flags(): every translation unit with compile-time switches reports them as "NAME=value " (stringified after expansion)
 #define UCNERF_STR2(x) #x
 #define UCNERF_STR(x) UCNERF_STR2(x)

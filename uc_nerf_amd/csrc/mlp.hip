@@ -623,6 +623,11 @@ int launch_pack_bf16_tab(const ucnerf_mlp_config* cfg, const ParamTable& t, cons
 int launch_mlp_fwd_bf16x3(const ucnerf_mlp_params* p, hipStream_t st);      // mlp_bf16.hip built with TERMS = 3
 int launch_mlp_fwd_bf16_plain(const ucnerf_mlp_params* p, hipStream_t st);   // ... and with TERMS = 1
 
+SplitGuard& split_guard() {
+    static thread_local SplitGuard g = {GUARD_NONE, nullptr};
+    return g;
+}
+
 const char* build_flags_mlp_f32() { return "mlp_f32: " UCNERF_FLAG(UCNERF_MLP_WAVES) UCNERF_FLAG(UCNERF_MLP_PRIO) UCNERF_FLAG(UCNERF_MLP_RING) UCNERF_FLAG(UCNERF_MLP_SAVE_NT); }
 
 }  // namespace ucnerf
@@ -713,6 +718,57 @@ int ucnerf_mlp_fwd(const ucnerf_mlp_params* p, void* stream) {
     if (p && (p->cfg.precision == 1 || p->cfg.precision == 3)) return launch_mlp_fwd_bf16x3(p, (hipStream_t)stream);      // (3: refused there with the reason)
     if (p && p->cfg.precision == 2) return launch_mlp_fwd_bf16_plain(p, (hipStream_t)stream);
     return launch_mlp_fwd(p, nullptr, (hipStream_t)stream);
+}
+
+// ---- the guarded split (include/ucnerf_hip.h): the existing calls with a status / condition word beside their parameters
+#define UCNERF_GUARD_ARGS(who, cfg_, word)                                                                                                    \
+    UCNERF_REQUIRE((cfg_) && (word), who ": null pointer (params / status word)");                                                            \
+    UCNERF_REQUIRE(((uintptr_t)(word) & 3) == 0, who ": the status word must be 4-byte aligned");                                            \
+    UCNERF_REQUIRE((cfg_)->precision >= 1 && (cfg_)->precision <= 3, who ": precision %d (the split precisions 1 .. 3 only)", (cfg_)->precision)
+#define UCNERF_GUARDED_ONLY(who, cfg_) \
+    UCNERF_REQUIRE((cfg_)->operand == 1, who ": cfg.operand %d (range detection belongs to the fp16 terms, operand 1)", (cfg_)->operand)
+
+int ucnerf_mlp_fwd_guarded(const ucnerf_mlp_params* p, uint32_t* status, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_fwd_guarded", p ? &p->cfg : nullptr, status);
+    UCNERF_GUARDED_ONLY("mlp_fwd_guarded", &p->cfg);
+    UCNERF_REQUIRE(p->m >= 0, "mlp_fwd_guarded: negative count %d", p->m);
+    SplitGuardScope scope(GUARD_DETECT, status);
+    return ucnerf_mlp_fwd(p, stream);
+}
+
+int ucnerf_mlp_fwd_if(const ucnerf_mlp_params* p, const uint32_t* run_if, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_fwd_if", p ? &p->cfg : nullptr, run_if);
+    UCNERF_REQUIRE(p->m >= 0, "mlp_fwd_if: negative count %d", p->m);
+    SplitGuardScope scope(GUARD_RUN_IF, const_cast<uint32_t*>(run_if));
+    return ucnerf_mlp_fwd(p, stream);
+}
+
+int ucnerf_mlp_pack_guarded(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, uint32_t* status, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_pack_guarded", cfg, status);
+    UCNERF_GUARDED_ONLY("mlp_pack_guarded", cfg);
+    SplitGuardScope scope(GUARD_DETECT, status);
+    return ucnerf_mlp_pack(cfg, flat, idx, out, stream);
+}
+
+int ucnerf_mlp_pack_if(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, const uint32_t* run_if, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_pack_if", cfg, run_if);
+    SplitGuardScope scope(GUARD_RUN_IF, const_cast<uint32_t*>(run_if));
+    return ucnerf_mlp_pack(cfg, flat, idx, out, stream);
+}
+
+int ucnerf_mlp_pack_tensors_guarded(const ucnerf_mlp_config* cfg, int32_t n_tensors, const void* const* tensor_ptrs_host, const int64_t* tensor_numel_host,
+                                    const int32_t* idx, float* out, uint32_t* status, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_pack_tensors_guarded", cfg, status);
+    UCNERF_GUARDED_ONLY("mlp_pack_tensors_guarded", cfg);
+    SplitGuardScope scope(GUARD_DETECT, status);
+    return ucnerf_mlp_pack_tensors(cfg, n_tensors, tensor_ptrs_host, tensor_numel_host, idx, out, stream);
+}
+
+int ucnerf_mlp_pack_tensors_if(const ucnerf_mlp_config* cfg, int32_t n_tensors, const void* const* tensor_ptrs_host, const int64_t* tensor_numel_host,
+                               const int32_t* idx, float* out, const uint32_t* run_if, void* stream) {
+    UCNERF_GUARD_ARGS("mlp_pack_tensors_if", cfg, run_if);
+    SplitGuardScope scope(GUARD_RUN_IF, const_cast<uint32_t*>(run_if));
+    return ucnerf_mlp_pack_tensors(cfg, n_tensors, tensor_ptrs_host, tensor_numel_host, idx, out, stream);
 }
 
 }  // extern "C"

@@ -57,30 +57,53 @@ namespace ucnerf {
 
 // ucnerf_mlp_config.operand (ABI v6): every build of this file exists twice -- with bf16 terms (UCNERF_OPERAND_FP16 = 0: the entry points below) and with
 // fp16 terms (UCNERF_OPERAND_FP16 = 1: 11-bit hi and lo terms, v_mfma_f32_32x32x16_f16; the same entry points under the suffix _h16, which the
-// bf16 build's entry points forward to when cfg.operand == 1).  fp16 has no range guard: values beyond 65 504 overflow.
+// bf16 build's entry points forward to when cfg.operand == 1).  These kernels do not watch fp16's range (values beyond 65 504 overflow); the UCNERF_SPLIT_GUARD builds below do.
 #ifndef UCNERF_OPERAND_FP16
 #define UCNERF_OPERAND_FP16 0
 #endif
+// The fp16-term builds exist once more with RANGE DETECTION compiled in (UCNERF_SPLIT_GUARD = 1, suffix _g16): every split of activations feeds a
+// per-lane running maximum of the |hi| halves, and a wave that saw fp16's largest finite value (|x| >= 65 504: conservative, clamping starts at
+// 131 008) ORs bit 0 into the caller's status word when it is done; the packers OR bit 1 for a weight whose hi term is not finite or reaches
+// 65 504.  All OTHER builds read the same kernel argument as `run_if`: when given, a block whose word reads zero returns at once -- the
+// conditional replay of a guarded launch on bf16 terms (ucnerf_*_guarded / ucnerf_*_if, include/ucnerf_hip.h).
+#ifndef UCNERF_SPLIT_GUARD
+#define UCNERF_SPLIT_GUARD 0
+#endif
+#if UCNERF_SPLIT_GUARD && !UCNERF_OPERAND_FP16
+#error "UCNERF_SPLIT_GUARD goes with UCNERF_OPERAND_FP16: bf16 terms have float32's range"
+#endif
 #if UCNERF_OPERAND_FP16
-#define build_pack_index_bf16 build_pack_index_bf16_h16
-#define launch_fused_tail launch_fused_tail_h16
-#define build_flags_mlp_bf16x3 build_flags_mlp_bf16x3_h16
-#define build_flags_mlp_bf16_plain build_flags_mlp_bf16_plain_h16
-#define launch_mlp_fwd_bf16x3 launch_mlp_fwd_bf16x3_h16
-#define launch_mlp_fwd_bf16x3_save launch_mlp_fwd_bf16x3_save_h16
-#define launch_mlp_fwd_bf16x3_gather launch_mlp_fwd_bf16x3_gather_h16
-#define launch_mlp_fwd_bf16_plain launch_mlp_fwd_bf16_plain_h16
-#define bf16_index_count bf16_index_count_h16
-#define bf16_stream_floats bf16_stream_floats_h16
-#define launch_pack_bf16 launch_pack_bf16_h16
-#define launch_pack_bf16_tab launch_pack_bf16_tab_h16
+#if UCNERF_SPLIT_GUARD
+#define UCNERF_SFX(name) name##_g16
+#else
+#define UCNERF_SFX(name) name##_h16
+#endif
+#define build_pack_index_bf16 UCNERF_SFX(build_pack_index_bf16)
+#define launch_fused_tail UCNERF_SFX(launch_fused_tail)
+#define build_flags_mlp_bf16x3 UCNERF_SFX(build_flags_mlp_bf16x3)
+#define build_flags_mlp_bf16_plain UCNERF_SFX(build_flags_mlp_bf16_plain)
+#define launch_mlp_fwd_bf16x3 UCNERF_SFX(launch_mlp_fwd_bf16x3)
+#define launch_mlp_fwd_bf16x3_save UCNERF_SFX(launch_mlp_fwd_bf16x3_save)
+#define launch_mlp_fwd_bf16x3_gather UCNERF_SFX(launch_mlp_fwd_bf16x3_gather)
+#define launch_mlp_fwd_bf16_plain UCNERF_SFX(launch_mlp_fwd_bf16_plain)
+#define bf16_index_count UCNERF_SFX(bf16_index_count)
+#define bf16_stream_floats UCNERF_SFX(bf16_stream_floats)
+#define launch_pack_bf16 UCNERF_SFX(launch_pack_bf16)
+#define launch_pack_bf16_tab UCNERF_SFX(launch_pack_bf16_tab)
+#if UCNERF_SPLIT_GUARD
+#define mlp_fwd_bf16_kernel mlp_fwd_g16_kernel
+#define pack_all_flat_kernel pack_all_flat_g16_kernel
+#define pack_all_tab_kernel pack_all_tab_g16_kernel
+#else
 #define mlp_fwd_bf16_kernel mlp_fwd_h16_kernel                      // (the kernels too: a template's instantiations are weak symbols -- the linker would keep ONE of two
 #define pack_all_flat_kernel pack_all_flat_h16_kernel                //  equally named ones and both operand kinds would run the same code)
 #define pack_all_tab_kernel pack_all_tab_h16_kernel
-#define UCNERF_OPERAND_DISPATCH(cfg_operand, call)
+#endif
+#define UCNERF_OPERAND_DISPATCH(cfg_operand, fn, ...)
 #else
-// (the fp16 build's entry points; `call` names one of them with this entry point's own arguments)
-#define UCNERF_OPERAND_DISPATCH(cfg_operand, call) do { if ((cfg_operand) == 1) return call; } while (0)
+// (the fp16 builds' entry points: `fn` with this entry point's own arguments, under _g16 when the calling entry point is a guarded one)
+#define UCNERF_OPERAND_DISPATCH(cfg_operand, fn, ...) \
+    do { if ((cfg_operand) == 1) return split_guard().mode == GUARD_DETECT ? fn##_g16(__VA_ARGS__) : fn##_h16(__VA_ARGS__); } while (0)
 #endif
 #if UCNERF_OPERAND_FP16
 typedef _Float16 op16;
@@ -244,21 +267,39 @@ typedef HiLo<op16x8> Frag;
 //  4 of 43 such cases above the 1e-4 bar; with the rounded hi the median error halves (2.9e-5 -> 1.9e-5, 90th percentile 9.3e-5 -> 4.7e-5)
 //  for +0.2 % of the headline kernel's time, profiles/r05_experiments.md.)
 typedef op16 op16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ Frag split8(const float (&x)[8]) {
+// GMax (UCNERF_SPLIT_GUARD builds; else nothing): the range flag of this WAVE -- non-zero once any of its lanes formed a saturated hi term.  Every
+// split8 call takes the per-lane maximum of the |hi| halves it packs (two 16-bit maxima in one short-lived register) and folds "some half reached the
+// limit" into this wave-uniform word, which lives in a scalar register.  (A per-lane maximum carried in a vector register through the whole tile
+// loop cost every instantiation 40 .. 120 spilled registers: the kernels have none to spare.)
+#if UCNERF_SPLIT_GUARD
+typedef unsigned GMax;
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+constexpr unsigned GUARD_HI_LIMIT = 0x7BFF;     // fp16's largest finite value: what the round-toward-zero conversion gives for every |x| >= 65 504
+#else
+struct GMax {};
+#endif
+__device__ __forceinline__ Frag split8(const float (&x)[8], GMax& gmax) {
     u32x4 hi;
     Frag f;
+#if UCNERF_SPLIT_GUARD
+    unsigned hmax = 0;
+#endif
 #if UCNERF_OPERAND_FP16 && !UCNERF_BF16_BUILD_TAIL
     const float minus_one = sopaque(-1.0f);
 #endif
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
 #if UCNERF_OPERAND_FP16
-        // fp16 terms: BOTH conversions toward zero (v_cvt_pkrtz_f16_f32) -- a value beyond fp16's range then becomes 65 504, never an infinity: an
+        // fp16 terms: BOTH conversions toward zero (v_cvt_pkrtz_f16_f32) -- an ACTIVATION beyond fp16's range then becomes 65 504, never an infinity (the packers of the weights make no such promise): an
         // activation past 131 008 is clamped (wrong, but finite: float32 itself resolves no more than 1e-2 of it), nothing ever turns into a NaN.
         // hi + lo holds 20 .. 21 bits (a rounded pair would hold 22).
         const auto hp = __builtin_amdgcn_cvt_pkrtz(x[j], x[j + 1]);
         const unsigned packed = __builtin_bit_cast(unsigned, hp);                 // [hi(x[j+1]) | hi(x[j])]
         hi[j >> 1] = packed;
+#if UCNERF_SPLIT_GUARD
+        // (a mask and ONE packed unsigned 16-bit maximum on the word already formed: no float compare, nothing read back from the accumulators)
+        hmax = j == 0 ? packed & 0x7fff7fffu : __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(u16x2, hmax), __builtin_bit_cast(u16x2, packed & 0x7fff7fffu)));
+#endif
         // x - (float)hi as ONE mixed-precision fma per value: v_fma_mix_f32 reads the fp16 half in place (no conversion back, no packed subtract: four
         // vector instructions per pair).  The compiler selects it only for a multiplier it cannot fold -- hence the opaque -1 in a scalar register; it
         // must be the COMPILER's instruction, not inline asm: the operands come out of MFMA accumulators and only the compiler's hazard recognizer
@@ -284,6 +325,12 @@ __device__ __forceinline__ Frag split8(const float (&x)[8]) {
 #endif
     }
     f.hi = __builtin_bit_cast(op16x8, hi);
+#if UCNERF_SPLIT_GUARD
+    {   // a half >= 0x7BFF  <=>  half + 0x0401 has bit 15 set (masked halves: no carry leaves a half); one integer compare for both halves
+        const unsigned over = __builtin_bit_cast(unsigned, __builtin_bit_cast(u16x2, hmax) + (u16x2){(unsigned short)(0x8000 - GUARD_HI_LIMIT), (unsigned short)(0x8000 - GUARD_HI_LIMIT)});
+        gmax |= __builtin_amdgcn_ballot_w64((over & 0x80008000u) != 0) != 0 ? 1u : 0u;
+    }
+#endif
     return f;
 }
 
@@ -317,7 +364,7 @@ __device__ __forceinline__ void save_tile(float* row, int nt, const f32x16& x) {
 // fragment s (0/1) of an accumulator tile: MODE 0 plain, 1 times m, 2 relu(times m)   (two values per v_pk_mul_f32);
 // SV: the eight fp32 values also go to `srow` (this lane's row of an activation set, NULL past the last sample) as row-tile nt
 template <int MODE, int SV = 0>       // SV: the kernel's SAVE (0 none, 1 fp32 sets, 2 24-bit sets)
-__device__ __forceinline__ Frag frag_of(const f32x16& a, const f32x16& m, int s, float* srow = nullptr, int nt = 0) {
+__device__ __forceinline__ Frag frag_of(GMax& gmax, const f32x16& a, const f32x16& m, int s, float* srow = nullptr, int nt = 0) {
     float t[8];
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -327,7 +374,7 @@ __device__ __forceinline__ Frag frag_of(const f32x16& a, const f32x16& m, int s,
         t[j + 1] = MODE == 2 ? fmaxf(v.y, 0.f) : v.y;
     }
     if (SV && srow) save8<SV == 2>(srow, nt, s, t);
-    Frag f = split8(t);
+    Frag f = split8(t, gmax);
     pin(f.hi); pin(f.lo);
     return f;
 }
@@ -552,7 +599,15 @@ template <bool TILED, int NSRC, int TERMS, int SAVE, bool FUSED = false, bool CO
 #ifndef UCNERF_BF16_WPS
 #define UCNERF_BF16_WPS 2      // waves per SIMD: 2 -> 256 VGPRs per wave, 1 -> 512
 #endif
-__global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(ucnerf_mlp_params p, BGeom g, int n_tiles, MlpSaved sv, FusedGather fg) {
+__global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(ucnerf_mlp_params p, BGeom g, int n_tiles, MlpSaved sv, FusedGather fg, unsigned* gword) {
+    // gword: UCNERF_SPLIT_GUARD builds -- the status word (never NULL: the launchers refuse that); all other builds -- `run_if`, NULL in every launch
+    // that is not a conditional replay: one uniform load and branch per block, before the block has touched LDS, a barrier or the weight stream
+#if UCNERF_SPLIT_GUARD
+    GMax gmax = 0;
+#else
+    GMax gmax;
+    if (gword && *gword == 0) return;
+#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];       // ONE shared object: [ring][constants][pe stash]
     // ring depth: the operand stash of seven and eight source views (FUSED) takes the room of two ring slots; a two-slot ring was measured
     // equal at full grids and 1.3 % slower on half-empty ones (profiles/r02_logs/r02_ring_two_slots.log)
@@ -920,7 +975,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
             float t[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] = pe[8 * q + e];
-            stash[q * 64] = split8(t);
+            stash[q * 64] = split8(t, gmax);
         }
     };
     if (FUSED) {                                            // (the gather itself opens every iteration of the tile loop)
@@ -974,7 +1029,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
                 float t[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) t[e] = pe[8 * q + e];
-                stash[q * 64] = split8(t);
+                stash[q * 64] = split8(t, gmax);
             }
         }
         __builtin_amdgcn_s_setprio(UCNERF_BF16_PRIO_GEMM);
@@ -983,12 +1038,12 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         init_bias_pair(cst, SEC_BD, h, 0, bd);
         init_bias_pair(cst, SEC_BD, h, 1, bd);
         {
-            Frag fc = split8(fsec[0]);
+            Frag fc = split8(fsec[0], gmax);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 if (q < kd16) {
                     Frag fn;
-                    HS(0, fc, bd[0], bd[1], if (q + 1 < 4 && q + 1 < kd16) { fn = split8(fsec[q + 1]); pin(fn.hi); pin(fn.lo); });
+                    HS(0, fc, bd[0], bd[1], if (q + 1 < 4 && q + 1 < kd16) { fn = split8(fsec[q + 1], gmax); pin(fn.hi); pin(fn.lo); });
                     HS(1, fc, bd[2], bd[3], if (q + 1 >= kd16) init_bias_pair(cst, SEC_L0, h, 0, acc));
                     if (q + 1 < 4 && q + 1 < kd16) fc = fn;
                 }
@@ -1011,7 +1066,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
                 const Frag b = pf;
                 HS(q & 1, b, acc[2], acc[3],
                    if (q < 3) pf = stash[(q + 1) * 64];
-                   X[q] = frag_of<2, SAVE>(acc[q >> 1], bd[q >> 1], q & 1, SAVE ? srow(sv.h[0]) : nullptr, q >> 1);
+                   X[q] = frag_of<2, SAVE>(gmax, acc[q >> 1], bd[q >> 1], q & 1, SAVE ? srow(sv.h[0]) : nullptr, q >> 1);
                    if (q == 3) init_bias_pair(cst, SEC_L0 + 1, h, 0, acc));
             }
         }
@@ -1024,12 +1079,12 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 HS(q & 1, in[q], acc[0], acc[1],
-                   if (q < 4) in[4 + q] = frag_of<2, SAVE>(acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1, SAVE ? srow(h_prev) : nullptr, 2 + (q >> 1));
+                   if (q < 4) in[4 + q] = frag_of<2, SAVE>(gmax, acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1, SAVE ? srow(h_prev) : nullptr, 2 + (q >> 1));
                    if (q == 4) init_bias_pair(cst, sec, h, 1, acc));
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 HS(q & 1, in[q], acc[2], acc[3],
-                   if (!(q & 1)) out[q >> 1] = frag_of<2, SAVE>(acc[q >> 2], bd[q >> 2], (q >> 1) & 1, SAVE ? srow(h_this) : nullptr, q >> 2);
+                   if (!(q & 1)) out[q >> 1] = frag_of<2, SAVE>(gmax, acc[q >> 2], bd[q >> 2], (q >> 1) & 1, SAVE ? srow(h_this) : nullptr, q >> 2);
                    if (q == 7) init_bias_pair(cst, sec + 1, h, 0, acc));
         };
 #pragma unroll 1
@@ -1052,7 +1107,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
             for (int q = 0; q < 12; ++q) {                                    // phase A
                 const Frag b = q < 4 ? X[q] : (q < 8 ? pf : X[q - 4]);
                 HS(q & 1, b, acc[0], acc[1],
-                   if (q < 4) X[4 + q] = frag_of<2, SAVE>(acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1, SAVE ? srow(sv.h[4]) : nullptr, 2 + (q >> 1));
+                   if (q < 4) X[4 + q] = frag_of<2, SAVE>(gmax, acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1, SAVE ? srow(sv.h[4]) : nullptr, 2 + (q >> 1));
                    if (q >= 3 && q < 7) pf = stash[(q - 3) * 64];
                    if (q == 4) init_bias_pair(cst, SEC_L0 + 5, h, 1, acc));
             }
@@ -1131,13 +1186,13 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         init_bias_pair(cst, SEC_BC, h, 0, bd);
         init_bias_pair(cst, SEC_BC, h, 1, bd);
         {
-            Frag fc = split8(fsec[0]);
+            Frag fc = split8(fsec[0], gmax);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 if (q < kc16) {
                     Frag fn;
                     HS(0, fc, bd[0], bd[1],
-                       if (q + 1 < 4 && q + 1 < kc16) { fn = split8(fsec[q + 1]); pin(fn.hi); pin(fn.lo); }
+                       if (q + 1 < 4 && q + 1 < kc16) { fn = split8(fsec[q + 1], gmax); pin(fn.hi); pin(fn.lo); }
                        if (q < 2) head_part(hbase, hb, h, acc[q], q, 0, 8, ident));
                     HS(1, fc, bd[2], bd[3],
                        if (q < 2) head_part(hbase, hb, h, acc[q], q, 8, 8, ident));
@@ -1151,14 +1206,14 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         }
         // g = h5 * b_c: fragments of row tiles 0,1 now, of 2,3 under feature_linear's phase A
 #pragma unroll
-        for (int q = 0; q < 4; ++q) X[q] = frag_of<1>(acc[q >> 1], bd[q >> 1], q & 1);
+        for (int q = 0; q < 4; ++q) X[q] = frag_of<1>(gmax, acc[q >> 1], bd[q >> 1], q & 1);
         init_bias_pair(cst, SEC_FT, h, 0, acc);
 
         // ---- feature_linear (pair-split); base heads of row tiles 2,3 underneath
 #pragma unroll
         for (int q = 0; q < 8; ++q)
             HS(q & 1, X[q], acc[0], acc[1],
-               if (q < 4) X[4 + q] = frag_of<1>(acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1);
+               if (q < 4) X[4 + q] = frag_of<1>(gmax, acc[2 + (q >> 1)], bd[2 + (q >> 1)], q & 1);
                if (q >= 4) head_part(hbase, hb, h, acc[2 + ((q - 4) >> 1)], 2 + ((q - 4) >> 1), (q & 1) * 8, 8, ident);
                if (q == 7) init_bias_pair(cst, SEC_FT, h, 1, acc);
                );
@@ -1168,7 +1223,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
 #pragma unroll
         for (int q = 0; q < 8; ++q)
             HS(q & 1, X[q], acc[2], acc[3],
-               if (!(q & 1)) Y[q >> 1] = frag_of<0, SAVE>(acc[q >> 2], acc[q >> 2], (q >> 1) & 1, SAVE ? srow(sv.ft) : nullptr, q >> 2);
+               if (!(q & 1)) Y[q >> 1] = frag_of<0, SAVE>(gmax, acc[q >> 2], acc[q >> 2], (q >> 1) & 1, SAVE ? srow(sv.ft) : nullptr, q >> 2);
                if (q & 1) {                                                    // direction encoding: 6 arguments, two per odd half-step
                    if (q < 7) {
                        const int hq_ = FUSED ? opaque(h) : h;           // (FUSED: keeps the per-lane frequency selects out of loop-long registers)
@@ -1187,13 +1242,13 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         for (int q = 0; q < 10; ++q) {
             const Frag b = q < 8 ? Y[q] : D[q - 8];
             HS(q & 1, b, acc[0], acc[1],
-               if (q < 4) Y[4 + q] = frag_of<0, SAVE>(acc[2 + (q >> 1)], acc[2 + (q >> 1)], q & 1, SAVE ? srow(sv.ft) : nullptr, 2 + (q >> 1));
+               if (q < 4) Y[4 + q] = frag_of<0, SAVE>(gmax, acc[2 + (q >> 1)], acc[2 + (q >> 1)], q & 1, SAVE ? srow(sv.ft) : nullptr, 2 + (q >> 1));
                if (q == 4) init_bias_pair(cst, SEC_VC, h, 1, acc);
                if (q == 5 || q == 6) {
                    float t[8];
                    _Pragma("unroll")
                    for (int e = 0; e < 8; ++e) t[e] = pd[8 * (q - 5) + e];
-                   D[q - 5] = split8(t); pin(D[q - 5].hi); pin(D[q - 5].lo);
+                   D[q - 5] = split8(t, gmax); pin(D[q - 5].hi); pin(D[q - 5].lo);
                }
                );
         }
@@ -1226,6 +1281,11 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         out.w = fmaxf(adapt.w * omu + base.w * u, 0.f);
         if (h == 0 && s_raw < s_lim) reinterpret_cast<f32x4*>(p.raw)[s_raw] = out;
     }
+#if UCNERF_SPLIT_GUARD
+    // once per wave, and only when one of its maxima reached the limit: ONE lane ORs bit 0 into the status word (a vector-memory atomic, retired by the
+    // vmcnt(0) below); a wave that saw nothing out of range writes nothing
+    if (gmax != 0 && lane == 0) atomicOr(gword, 1u);
+#endif
     wait_vmcnt<0>();       // no LDS-DMA may outlive the workgroup's LDS allocation
     if (TAIL) {
         // ---- K7 (+ K8, K9) of this block's rays.  Every output of every tile of these rays was stored by a wave of THIS block: the stores have been
@@ -1270,6 +1330,7 @@ static_assert(bf16_smem_bytes_fused(6) <= 160 * 1024 && bf16_smem_bytes_fused(8)
 int launch_fused_tail(const ucnerf_mlp_params* p, const BGeom* g, int n_tiles, const FusedGather* fg, int blocks, hipStream_t st) {
     MlpSaved sv;
     memset(&sv, 0, sizeof(sv));
+    unsigned* const gword = split_guard().word;          // (checked by launch_bf16, this launcher's only caller)
     const int v = p->cfg.n_src;
     const size_t smem_f = bf16_smem_bytes_fused(v);
     static_assert(BW * (sizeof(PdfShared<128, 512>) + (128 + 2) * sizeof(float)) <= bf16_smem_bytes_fused(1), "the rays' LDS arrays re-use the kernel's image");
@@ -1278,12 +1339,12 @@ int launch_fused_tail(const ucnerf_mlp_params* p, const BGeom* g, int n_tiles, c
     if (v == N && !fg->pts_in) {                                                                                               \
         const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>;                 \
         if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, compositing in the tail)")) return rc; \
-        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg); \
+        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg, gword); \
     }                                                                                                                          \
     if (v == N && fg->pts_in) {      /* coordinates given: what rendering() hands over (network/renderer.py:215-255) */       \
         const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>;                  \
         if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, given coordinates, compositing in the tail)")) return rc; \
-        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg); \
+        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg, gword); \
     }
     X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
 #undef X
@@ -1303,6 +1364,12 @@ static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStre
     UCNERF_REQUIRE(((uintptr_t)p->wstream & 15) == 0 && ((uintptr_t)p->raw & 15) == 0, "mlp_fwd: wstream/raw must be 16-byte aligned");
     Bf16Layout B;
     UCNERF_REQUIRE(bf16_layout(p->cfg.n_src, &B), "mlp_fwd: n_src %d outside 1..8", p->cfg.n_src);
+    // the guarded split: this build's kernels take the status word (UCNERF_SPLIT_GUARD) or the optional condition word of a replay
+    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0), "mlp_fwd: range detection is compiled into the guarded fp16-term "
+                   "kernels only (ucnerf_*_guarded with cfg.operand 1)");
+    UCNERF_REQUIRE(split_guard().mode == GUARD_NONE || (split_guard().word && !save), "mlp_fwd: a guarded or conditional launch needs its status word "
+                   "and serves the inference forward");
+    unsigned* const gword = split_guard().word;
     const int n_tiles = cdiv(p->m, 32);
     const int cus = device_cus();
     if (cus <= 0) return fail(UCNERF_EHIP, "mlp_fwd: no device");
@@ -1344,17 +1411,17 @@ static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStre
         if (B.v == N && !fg.pts_in && fg.s16) {                                                                                \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>;                           \
             if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, bf16 sources)")) return rc;      \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg); \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
         }                                                                                                                      \
         if (B.v == N && !fg.pts_in && !fg.s16 && !fg.gen_xs) {                                                                 \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true>;                                        \
             if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused)")) return rc;                    \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg); \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
         }                                                                                                                      \
         if (B.v == N && fg.pts_in) {                                                                                           \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, true>;                                  \
             if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, given coordinates)")) return rc; \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg); \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
         }
         UCNERF_BF16_FOR_ALL(X)
 #undef X
@@ -1363,7 +1430,7 @@ static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStre
         if (B.v == N && fg.gen_xs) {                                                                                           \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>;                    \
             if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, rays generated)")) return rc;    \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg); \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
         }
         X(1) X(2) X(3) X(4) X(5) X(6)
 #undef X
@@ -1376,17 +1443,17 @@ static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStre
         if (B.v == N && !tiled && !sv.p24) {                                                                                   \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<false, N, 3, 1>;                                                 \
             if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3)")) return rc;                              \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 1>), grid, block, smem, st, *p, g, n_tiles, sv, fg);              \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 1>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);              \
         }                                                                                                                      \
         if (B.v == N && !tiled && sv.p24) {                                                                                    \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<false, N, 3, 2>;                                                 \
             if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3, 24-bit sets)")) return rc;                 \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg);              \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);              \
         }                                                                                                                      \
         if (B.v == N && tiled) {                                                                                               \
             const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, 2>;                                                  \
             if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3, tiled features, 24-bit sets)")) return rc; \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg);               \
+            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);               \
         }
         UCNERF_BF16_FOR_ALL(X)
 #undef X
@@ -1399,8 +1466,8 @@ static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStre
     if (B.v == N) {                                                                                                            \
         const void* fn = tiled ? (const void*)mlp_fwd_bf16_kernel<true, N, K, false> : (const void*)mlp_fwd_bf16_kernel<false, N, K, false>; \
         if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd (bf16)")) return rc;                                          \
-        if (tiled) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg);    \
-        else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg);         \
+        if (tiled) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);    \
+        else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);         \
     }
     UCNERF_BF16_FOR_ALL(X)
 #undef X
@@ -1425,11 +1492,16 @@ int launch_mlp_fwd_bf16x3_gather_h16(const ucnerf_render_params* rp, const float
                                      const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out);
 int launch_pack_bf16_h16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st);
 int launch_pack_bf16_tab_h16(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st);
+int launch_mlp_fwd_bf16x3_g16(const ucnerf_mlp_params* p, hipStream_t st);                   // ... and their twins with range detection (UCNERF_SPLIT_GUARD)
+int launch_mlp_fwd_bf16x3_gather_g16(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st, const ucnerf_composite_params* tail_c,
+                                     const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out);
+int launch_pack_bf16_g16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st);
+int launch_pack_bf16_tab_g16(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st);
 #endif
 int launch_mlp_fwd_bf16x3(const ucnerf_mlp_params* p, hipStream_t st) {
     UCNERF_REQUIRE(p, "mlp_fwd: null params");
     UCNERF_REQUIRE(p->cfg.operand == 0 || p->cfg.operand == 1, "mlp_fwd: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", p->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16x3_h16(p, st));
+    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16x3, p, st);
     return launch_bf16(p, nullptr, st);
 }
 int launch_mlp_fwd_bf16x3_save(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st) {
@@ -1444,7 +1516,7 @@ int check_cl_sources(const ucnerf_render_params* p, const char* who);      // ga
 int launch_mlp_fwd_bf16x3_gather(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st,
                                  const ucnerf_composite_params* tail_c, const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out) {
     UCNERF_REQUIRE(rp->cfg.operand == 0 || rp->cfg.operand == 1, "render (gather fused): cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", rp->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(rp->cfg.operand, launch_mlp_fwd_bf16x3_gather_h16(rp, dirs, raw, st, tail_c, tail_s, tail_dir_out));
+    UCNERF_OPERAND_DISPATCH(rp->cfg.operand, launch_mlp_fwd_bf16x3_gather, rp, dirs, raw, st, tail_c, tail_s, tail_dir_out);
     const long long M = (long long)rp->n * rp->S;
     UCNERF_REQUIRE(M < (1ll << 31), "render (gather fused): %lld samples in one pass (limit 2^31 - 1)", M);
     if (int rc = check_cl_sources(rp, "render (gather fused)")) return rc;
@@ -1497,11 +1569,12 @@ int launch_mlp_fwd_bf16x3_gather(const ucnerf_render_params* rp, const float* di
 #else
 #if !UCNERF_OPERAND_FP16
 int launch_mlp_fwd_bf16_plain_h16(const ucnerf_mlp_params* p, hipStream_t st);
+int launch_mlp_fwd_bf16_plain_g16(const ucnerf_mlp_params* p, hipStream_t st);
 #endif
 int launch_mlp_fwd_bf16_plain(const ucnerf_mlp_params* p, hipStream_t st) {
     UCNERF_REQUIRE(p, "mlp_fwd: null params");
     UCNERF_REQUIRE(p->cfg.operand == 0 || p->cfg.operand == 1, "mlp_fwd: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", p->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16_plain_h16(p, st));
+    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16_plain, p, st);
     return launch_bf16(p, nullptr, st);
 }
 #endif
@@ -1521,8 +1594,20 @@ int64_t bf16_stream_floats(const ucnerf_mlp_config* cfg) {
 
 // ONE launch for the whole stream from the flat parameter vector (round 5: the evaluation loop re-packs in every rendering() call -- two launches were
 // 5 us of GPU time and two launches' host time per 1024-pixel chunk): blocks [0, nb16) convert the bf16 half-steps, the rest copy the fp32 constants
+// gword: as in mlp_fwd_bf16_kernel -- `run_if` (NULL in an unconditional pack), or the status word of the guarded fp16 packers, which OR bit 1 into it
+// for a weight whose hi term is not finite or reaches 65 504 (the unguarded fp16 packers turn such a weight into hi = inf, lo = -inf)
+#if UCNERF_SPLIT_GUARD
+__device__ __forceinline__ void guard_weight(op16 hi, unsigned* gword) {
+    if ((__builtin_bit_cast(unsigned short, hi) & 0x7fffu) >= GUARD_HI_LIMIT) atomicOr(gword, 2u);      // (a vector-memory atomic of the lanes concerned; 65 504, inf, NaN)
+}
+#else
+#define UCNERF_RUN_IF(gword) do { if ((gword) && *(gword) == 0) return; } while (0)
+#endif
 __global__ void pack_all_flat_kernel(const float* __restrict__ flat, const int32_t* __restrict__ idx, unsigned short* __restrict__ out16, int64_t n16,
-                                     float* __restrict__ outc, int nc, int nb16) {
+                                     float* __restrict__ outc, int nc, int nb16, unsigned* gword) {
+#if !UCNERF_SPLIT_GUARD
+    UCNERF_RUN_IF(gword);
+#endif
     if ((int)blockIdx.x < nb16) {
         const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         if (i >= n16) return;
@@ -1531,6 +1616,9 @@ __global__ void pack_all_flat_kernel(const float* __restrict__ flat, const int32
         if (k >= 0) {
             const float w = flat[k & 0x3fffffff];
             const op16 hi = (op16)w;
+#if UCNERF_SPLIT_GUARD
+            if (!(k >> 30)) guard_weight(hi, gword);
+#endif
             const op16 val = (k >> 30) ? (op16)(w - (float)hi) : hi;
             r = __builtin_bit_cast(unsigned short, val);
         }
@@ -1543,18 +1631,24 @@ __global__ void pack_all_flat_kernel(const float* __restrict__ flat, const int32
 
 int launch_pack_bf16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st) {
     UCNERF_REQUIRE(cfg->operand == 0 || cfg->operand == 1, "mlp_pack: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", cfg->operand);
-    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16_h16(cfg, flat, idx, out, st));
+    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16, cfg, flat, idx, out, st);
     Bf16Layout B;
     UCNERF_REQUIRE(bf16_layout(cfg->n_src, &B), "mlp_pack: n_src %d outside 1..8", cfg->n_src);
+    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0) && (split_guard().mode == GUARD_NONE || split_guard().word),
+                   "mlp_pack: range detection is compiled into the guarded fp16 packers only (ucnerf_mlp_pack*_guarded with cfg.operand 1), with a status word");
     const int64_t n16 = (int64_t)B.slots * (SLOT_BYTES / 2);
     const int nb16 = cdiv(n16, 256), nbc = cdiv(CONST_FLOATS, 256);
     hipLaunchKernelGGL(pack_all_flat_kernel, dim3(nb16 + nbc), dim3(256), 0, st, flat, idx, reinterpret_cast<unsigned short*>(out), n16,
-                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16);
+                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16, split_guard().word);
     return check_launch("mlp_pack (bf16x3)");
 }
 
 // ONE launch for the whole stream (the drop-in re-packs in every no_grad call): blocks [0, nb16) convert the bf16 half-steps, the rest copy the fp32 constants
-__global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ idx, unsigned short* __restrict__ out16, int64_t n16, float* __restrict__ outc, int nc, int nb16) {
+__global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ idx, unsigned short* __restrict__ out16, int64_t n16, float* __restrict__ outc, int nc, int nb16,
+                                    unsigned* gword) {
+#if !UCNERF_SPLIT_GUARD
+    UCNERF_RUN_IF(gword);
+#endif
     __shared__ ParamTableLds l;
     param_table_to_lds(t, &l);
     if ((int)blockIdx.x < nb16) {
@@ -1565,6 +1659,9 @@ __global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ id
         if (k >= 0) {
             const float w = param_table_load(&l, k & 0x3fffffff);
             const op16 hi = (op16)w;
+#if UCNERF_SPLIT_GUARD
+            if (!(k >> 30)) guard_weight(hi, gword);
+#endif
             const op16 val = (k >> 30) ? (op16)(w - (float)hi) : hi;
             r = __builtin_bit_cast(unsigned short, val);
         }
@@ -1577,13 +1674,15 @@ __global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ id
 
 int launch_pack_bf16_tab(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st) {
     UCNERF_REQUIRE(cfg->operand == 0 || cfg->operand == 1, "mlp_pack_tensors: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", cfg->operand);
-    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16_tab_h16(cfg, t, idx, out, st));
+    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16_tab, cfg, t, idx, out, st);
     Bf16Layout B;
     UCNERF_REQUIRE(bf16_layout(cfg->n_src, &B), "mlp_pack: n_src %d outside 1..8", cfg->n_src);
+    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0) && (split_guard().mode == GUARD_NONE || split_guard().word),
+                   "mlp_pack: range detection is compiled into the guarded fp16 packers only (ucnerf_mlp_pack*_guarded with cfg.operand 1), with a status word");
     const int64_t n16 = (int64_t)B.slots * (SLOT_BYTES / 2);
     const int nb16 = cdiv(n16, 256), nbc = cdiv(CONST_FLOATS, 256);
     hipLaunchKernelGGL(pack_all_tab_kernel, dim3(nb16 + nbc), dim3(256), 0, st, t, idx, reinterpret_cast<unsigned short*>(out), n16,
-                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16);
+                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16, split_guard().word);
     return check_launch("mlp_pack_tensors (bf16x3)");
 }
 

@@ -196,6 +196,11 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
         s_res = *p->resample;
         s_res.weights = nullptr; s_res.z_merge = p->z;
     }
+    // the guarded split (ucnerf_render_fused_fwd_guarded / _if): the MLP launch of the pass carries the call's status / condition word.  A conditional
+    // replay (`replay`) repeats the WHOLE pass from the same inputs -- nothing the first call wrote is an input of the pass -- so its other launches
+    // (directions, gather, compositing, re-sampling) run unconditionally and, when the MLP launch is skipped, rewrite the bits that are there
+    const bool replay = split_guard().mode == GUARD_RUN_IF;
+    UCNERF_REQUIRE(split_guard().mode == GUARD_NONE || !p->train_workspace, "render_fused_fwd: the guarded split serves the inference forward");
     if (p->cfg.precision == 3) {                        // row f1: gather + PE + MLP in one launch, no feature buffer at all
         UCNERF_REQUIRE(cl_given(p) && !keep_feats && !p->u_sampled && !p->train_workspace,
                        "render_fused_fwd: precision 3 (gather fused into the MLP kernel) needs the channel-last sources; it keeps no features "
@@ -207,14 +212,14 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
         const bool dirs_in_tail = tail && !gen && !p->dir_feat && p->w2c_dir_dev;
         if (!gen && !p->dir_feat && !dirs_in_tail && (rc = launch_dirs(p, st, w))) return rc;
         raw_fused = p->raw ? p->raw : w->raw;
-        if (p->ev_mlp_start && (rc = ucnerf_event_record(p->ev_mlp_start, st))) return rc;
+        if (p->ev_mlp_start && !replay && (rc = ucnerf_event_record(p->ev_mlp_start, st))) return rc;
         if (tail) composite_args(p, raw_fused, &c);
         // (rays generated inside the launch: the RAYGEN instantiation derives every lane's direction feature itself and uses w->angle as scratch; the
         //  tail route's blocks write the caller's buffers first and read them like given ones)
         if ((rc = launch_mlp_fwd_bf16x3_gather(p, gen && !tail ? w->angle : p->dir_feat ? p->dir_feat : w->angle, raw_fused, st, tail ? &c : nullptr,
                                                tail && p->resample ? &s_res : nullptr, dirs_in_tail ? w->angle : nullptr))) return rc;
-        if (p->ev_mlp_stop && (rc = ucnerf_event_record(p->ev_mlp_stop, st))) return rc;
-        if (tail) { ++g_tail_launches; return UCNERF_OK; }      // K7 (and K8, K9) ran inside the launch
+        if (p->ev_mlp_stop && !replay && (rc = ucnerf_event_record(p->ev_mlp_stop, st))) return rc;
+        if (tail) { if (!replay) ++g_tail_launches; return UCNERF_OK; }      // K7 (and K8, K9) ran inside the launch
     } else if (cl_given(p)) {                                  // fast path: channel-last sources, coordinates derived in-kernel
         g.out_tiled = keep_feats ? (p->feats_tiled ? 1 : 0) : 1;
         g.feats = keep_feats ? p->feats : w->feats;
@@ -234,14 +239,14 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
         if (!p->dir_feat && (rc = launch_dirs(p, st, w))) return rc;
         mlp_args(p, w, g.feats, g.out_tiled, p->raw ? p->raw : w->raw, &m);
         if (p->dir_feat) m.dirs = p->dir_feat;
-        if (p->ev_mlp_start && (rc = ucnerf_event_record(p->ev_mlp_start, st))) return rc;
+        if (p->ev_mlp_start && !replay && (rc = ucnerf_event_record(p->ev_mlp_start, st))) return rc;
         if (p->train_workspace && keep_feats && p->raw) {    // training forward: activations go straight into the backward's workspace
             Workspace wb;
             float *g_raw, *g_feats, *mlp_ws;
             carve_bwd_render(p->train_workspace, p->n, p->S, V, &wb, &g_raw, &g_feats, &mlp_ws);
             if ((rc = ucnerf_mlp_fwd_train(&m, mlp_ws, p->train_bwd_mode, st))) return rc;
         } else if ((rc = ucnerf_mlp_fwd(&m, st))) return rc;
-        if (p->ev_mlp_stop && (rc = ucnerf_event_record(p->ev_mlp_stop, st))) return rc;
+        if (p->ev_mlp_stop && !replay && (rc = ucnerf_event_record(p->ev_mlp_stop, st))) return rc;
     }
 
     composite_args(p, m.raw, &c);
@@ -349,6 +354,24 @@ int ucnerf_render_fused_fwd(const ucnerf_render_params* p, void* stream) {
     }
     Workspace w;
     return run_forward(p, (hipStream_t)stream, &w);
+}
+
+// ---- the guarded split (include/ucnerf_hip.h)
+int ucnerf_render_fused_fwd_guarded(const ucnerf_render_params* p, uint32_t* status, void* stream) {
+    UCNERF_REQUIRE(p && status, "render_fused_fwd_guarded: null pointer (params / status word)");
+    UCNERF_REQUIRE(((uintptr_t)status & 3) == 0, "render_fused_fwd_guarded: the status word must be 4-byte aligned");
+    UCNERF_REQUIRE(p->cfg.precision >= 1 && p->cfg.precision <= 3 && p->cfg.operand == 1, "render_fused_fwd_guarded: precision %d, operand %d (range "
+                   "detection belongs to the fp16 terms of the split precisions: precision 1 .. 3, operand 1)", p->cfg.precision, p->cfg.operand);
+    SplitGuardScope scope(GUARD_DETECT, status);
+    return ucnerf_render_fused_fwd(p, stream);
+}
+
+int ucnerf_render_fused_fwd_if(const ucnerf_render_params* p, const uint32_t* run_if, void* stream) {
+    UCNERF_REQUIRE(p && run_if, "render_fused_fwd_if: null pointer (params / condition word)");
+    UCNERF_REQUIRE(((uintptr_t)run_if & 3) == 0, "render_fused_fwd_if: the condition word must be 4-byte aligned");
+    UCNERF_REQUIRE(p->cfg.precision >= 1 && p->cfg.precision <= 3, "render_fused_fwd_if: precision %d (the split precisions 1 .. 3 only)", p->cfg.precision);
+    SplitGuardScope scope(GUARD_RUN_IF, const_cast<uint32_t*>(run_if));
+    return ucnerf_render_fused_fwd(p, stream);
 }
 
 }  // extern "C"

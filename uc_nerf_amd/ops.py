@@ -611,7 +611,8 @@ def set_backward_mode(mode):
     _backward_mode = BACKWARD_MODES[mode]
 
 
-SPLIT_OPERANDS = {"bf16": 0, "fp16": 1}
+# (2 is this module's own code for the guarded mode: the ABI knows operands 0 and 1 -- the guard is a property of the call, PackedWeights.guarded)
+SPLIT_OPERANDS = {"bf16": 0, "fp16": 1, "fp16_guarded": 2}
 _split_operand = SPLIT_OPERANDS[os.environ.get("UCNERF_SPLIT_OPERAND", "bf16")]
 
 
@@ -619,16 +620,73 @@ def set_split_operand(kind):
     """The 16-bit terms of the split precisions ("bf16x3", "bf16x3_fused", "bf16") from now on (ucnerf_mlp_config.operand, ABI v6): "bf16" (default:
     8 significant bits per term, float32's range) or "fp16" (11 bits per term at the same matrix-core rate -- the three-product split then holds ~22
     bits and the renders sit at float32 level, no measurable kernel time (+0.1 %) -- but fp16's range: an activation beyond 131 008 is clamped, a term below 6e-5 is held
-    to 3e-8 absolute).  Takes effect
-    for every weight stream packed afterwards (PackedWeights.get keys on it); inference only."""
+    to 3e-8 absolute; a WEIGHT beyond 65 504 packs to infinities and renders NaN).  Takes effect
+    for every weight stream packed afterwards (PackedWeights.get keys on it); inference only.
+
+    "fp16_guarded": the fp16 terms with their range watched on the device.  Every pack and every no_grad launch runs kernels that compute exactly
+    what "fp16" computes and OR a bit into a per-device status word when a value left fp16's safe range (bit 0: an activation or input with
+    |x| >= 65 504 -- conservative, clamping starts at 131 008; bit 1: a weight whose hi term is not finite or reaches 65 504).  Directly behind each
+    such launch, and before anything consumes its outputs, the same pass is enqueued once more on bf16 terms under `run_if = status`: its kernels return
+    at once while the word is zero.  No host synchronisation; the outputs of a call are bit-identical to "fp16" when nothing saturated and to "bf16"
+    when something did.  The word is STICKY -- the library never clears it, so after one saturated call every later call replays (and equals "bf16")
+    until split_guard_clear(): the safe direction.  Not caught, and unchanged from "fp16": terms below 6e-5 lose relative precision (they stay
+    within the absolute bar).  Cost: the range checks (a few vector instructions per split), one skipped launch per pass, and a pass's bf16 time
+    on top when it does replay.  A weight stream holds both term kinds (twice the floats)."""
     global _split_operand
     if kind not in SPLIT_OPERANDS:
-        raise ValueError("uc_nerf_amd: split operand must be 'bf16' or 'fp16', got %r" % (kind,))
+        raise ValueError("uc_nerf_amd: split operand must be 'bf16', 'fp16' or 'fp16_guarded', got %r" % (kind,))
     _split_operand = SPLIT_OPERANDS[kind]
 
 
 def split_operand():
-    return "fp16" if _split_operand else "bf16"
+    return ("bf16", "fp16", "fp16_guarded")[_split_operand]
+
+
+# one status word per device of the guarded split, allocated once and kept for the life of the process: captured graphs hold its address
+_guard_words = {}
+
+
+def _guard_word(device):
+    device = torch.device(device)
+    idx = device.index if device.index is not None else _cur_dev()
+    w = _guard_words.get(idx)
+    if w is None:
+        w = _guard_words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return w
+
+
+def split_guard_status(clear=False, device=None):
+    """The guarded split's status word of `device` (default: the current one) as an int: bit 0 = an activation or input reached 65 504 in a
+    "fp16_guarded" launch, bit 1 = a weight did in a pack; 0 = every call since the last clear ran on fp16 terms.  SYNCHRONISES (reads the word back);
+    clear=True also zeroes it afterwards.  The word is sticky: while it is non-zero every guarded call replays on bf16 terms."""
+    w = _guard_word(device if device is not None else torch.device("cuda", _cur_dev()))
+    v = int(w.item()) & 0xffffffff
+    if clear:
+        w.zero_()
+    return v
+
+
+def split_guard_clear(device=None):
+    """Enqueues a clear of the status word on the current stream (no synchronisation): calls enqueued afterwards run on fp16 terms again."""
+    _guard_word(device if device is not None else torch.device("cuda", _cur_dev())).zero_()
+
+
+def _launch_split(pw, name, params, device):
+    """_launch for the entry points that run the network (`params`: .cfg and .wstream): in the guarded mode the fp16 launch with range detection, then
+    the same call on the bf16 half of the stream under run_if = the status word -- same stream, same inputs, before anything reads the outputs."""
+    if not pw.guarded:
+        return _launch(name, params, device)
+    word = _ptr(_guard_word(device))
+    lib = L.lib()
+    ws = params.wstream
+    with _on(device):
+        st = C.c_void_p(_stream())
+        L.check(getattr(lib, name + "_guarded")(C.addressof(params), C.c_void_p(word), st), name + "_guarded")
+        params.cfg.operand, params.wstream = 0, ws + 4 * pw.n_stream_terms
+        try:
+            L.check(getattr(lib, name + "_if")(C.addressof(params), C.c_void_p(word), st), name + "_if")
+        finally:
+            params.cfg.operand, params.wstream = 1, ws
 
 
 class PackedWeights:
@@ -638,11 +696,19 @@ class PackedWeights:
     PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2, "bf16x3_fused": 3}     # 3: bf16x3 with the gather inside the MLP kernel (render passes only)
 
     def __init__(self, n_src, pe_layout, device, precision="f32", operand=0):
-        self.cfg = L.MlpConfig(n_src, pe_layout, self.PRECISIONS[precision], 0 if precision == "f32" else int(operand))
-        self.precision, self.operand = precision, self.cfg.operand
+        operand = 0 if precision == "f32" else int(operand)
+        # operand 2 = "fp16_guarded": the ABI's operand 1 with guarded calls; the stream is [fp16 terms | bf16 terms], the second half for the replay
+        self.guarded = operand == 2
+        self.cfg = L.MlpConfig(n_src, pe_layout, self.PRECISIONS[precision], 1 if self.guarded else operand)
+        self.precision, self.operand = precision, operand
         lib = L.lib()
         self.n_params = lib.ucnerf_mlp_param_count(C.addressof(self.cfg))
-        self.n_stream = lib.ucnerf_mlp_stream_count(C.addressof(self.cfg))
+        self.n_stream_terms = lib.ucnerf_mlp_stream_count(C.addressof(self.cfg))       # floats of ONE term kind's stream (the same for both kinds)
+        self.n_stream = self.n_stream_terms * (2 if self.guarded else 1)
+        if self.guarded:
+            self.cfg_bf16 = L.MlpConfig(n_src, pe_layout, self.PRECISIONS[precision], 0)
+            if torch.device(device).type == "cuda":
+                _guard_word(device)                     # (made here: never inside a graph capture)
         n_idx = lib.ucnerf_mlp_index_count(C.addressof(self.cfg))
         if self.n_params < 0 or self.n_stream < 0 or n_idx < 0:
             raise RuntimeError("uc_nerf_amd: unsupported MLP config n_src=%d precision=%s: %s"
@@ -655,7 +721,7 @@ class PackedWeights:
 
     @classmethod
     def get(cls, n_src, pe_layout, device, precision="f32", operand=None):
-        """operand: None = the module's current setting (set_split_operand); "bf16" / "fp16" / 0 / 1 to pin it."""
+        """operand: None = the module's current setting (set_split_operand); "bf16" / "fp16" / "fp16_guarded" / 0 / 1 / 2 to pin it."""
         op = _split_operand if operand is None else SPLIT_OPERANDS.get(operand, operand)
         op = 0 if precision == "f32" else int(op)
         key = (n_src, pe_layout, str(device), precision, op)
@@ -674,8 +740,21 @@ class PackedWeights:
         elif out.numel() != self.n_stream or out.dtype != torch.float32 or not out.is_contiguous() or out.device != flat.device:
             raise RuntimeError("uc_nerf_amd: stream buffer must be %d contiguous float32 on the parameters' device" % self.n_stream)
         with _on(flat.device):
-            L.check(L.lib().ucnerf_mlp_pack(C.addressof(self.cfg), _ptr(flat), _ptr(self.idx), _ptr(out), _stream()), "ucnerf_mlp_pack")
+            if self.guarded:
+                self._pack_guarded("ucnerf_mlp_pack", (_ptr(flat),), out)
+            else:
+                L.check(L.lib().ucnerf_mlp_pack(C.addressof(self.cfg), _ptr(flat), _ptr(self.idx), _ptr(out), _stream()), "ucnerf_mlp_pack")
         return out
+
+    def _pack_guarded(self, name, src_args, out):
+        """The guarded fp16 pack into the first half of `out`, the bf16 pack into the second.  The bf16 half is packed UNCONDITIONALLY (the plain
+        entry point, not ucnerf_*_pack*_if under the status word): a launch that saturates later -- an activation, with finite weights -- replays
+        against this half, so it has to be there whatever the word reads at pack time."""
+        lib, st = L.lib(), C.c_void_p(_stream())
+        idx, o = C.c_void_p(_ptr(self.idx)), _ptr(out)
+        L.check(getattr(lib, name + "_guarded")(C.addressof(self.cfg), *src_args, idx, C.c_void_p(o), C.c_void_p(_ptr(_guard_word(out.device))), st),
+                name + "_guarded")
+        L.check(getattr(lib, name)(C.addressof(self.cfg_bf16), *src_args, idx, C.c_void_p(o + 4 * self.n_stream_terms), st), name)
 
     def pack_table(self, table, out):
         """Packs the stream straight from separate parameter tensors (TensorTable) into `out`, in place: one launch, no concatenation."""
@@ -684,8 +763,11 @@ class PackedWeights:
         if out.numel() != self.n_stream or out.dtype != torch.float32 or not out.is_contiguous():
             raise RuntimeError("uc_nerf_amd: stream buffer must be %d contiguous float32" % self.n_stream)
         with _on(out.device):
-            L.check(L.lib().ucnerf_mlp_pack_tensors(C.addressof(self.cfg), table.n, table.ptrs, table.numel, _ptr(self.idx), _ptr(out), _stream()),
-                    "ucnerf_mlp_pack_tensors")
+            if self.guarded:
+                self._pack_guarded("ucnerf_mlp_pack_tensors", (table.n, table.ptrs, table.numel), out)
+            else:
+                L.check(L.lib().ucnerf_mlp_pack_tensors(C.addressof(self.cfg), table.n, table.ptrs, table.numel, _ptr(self.idx), _ptr(out), _stream()),
+                        "ucnerf_mlp_pack_tensors")
         return out
 
     def unpack_grad(self, g_stream):
@@ -733,7 +815,7 @@ def mlp_fwd(pw, wstream, pts, dirs, feats, S, feats_tiled=False, max_blocks=0):
     p.feats_tiled, p.max_blocks = int(feats_tiled), int(max_blocks)
     raw = torch.empty(m, 4, device=pts.device)
     p.pts, p.dirs, p.feats, p.wstream, p.raw = _ptr(pts), _ptr(dirs), _ptr(feats), _ptr(wstream), _ptr(raw)
-    _launch("ucnerf_mlp_fwd", p, pts.device)
+    _launch_split(pw, "ucnerf_mlp_fwd", p, pts.device)
     return raw
 
 
@@ -843,7 +925,7 @@ def mlp_fwd_encoded(pw, wstream, x):
     _encoded_params(p, pw, x)
     raw = torch.empty(x.shape[0], 4, device=x.device)
     p.wstream, p.raw = _ptr(wstream), _ptr(raw)
-    _launch("ucnerf_mlp_fwd", p, x.device)
+    _launch_split(pw, "ucnerf_mlp_fwd", p, x.device)
     return raw
 
 
@@ -1287,7 +1369,7 @@ class RenderPass:
             p.train_workspace = _ptr(self._bwd_ws)
             p.train_bwd_mode = _backward_mode          # (fixes the format the activations are kept in: 24-bit for the chain, fp32 layer by layer)
             self._saved_for = (n, S, out["raw"].data_ptr(), _backward_mode)
-        _launch("ucnerf_render_fused_fwd", p, dev)
+        _launch_split(self.pw, "ucnerf_render_fused_fwd", p, dev)
         return out
 
     def saved_matches(self, n, S, raw):
