@@ -560,6 +560,40 @@ typedef struct {
 } ucnerf_depth_regress_bwd_params;
 int ucnerf_depth_regress_bwd(const ucnerf_depth_regress_bwd_params* p, void* stream);
 
+/* The link between two cascade stages (added to ABI v6; nothing above moved): the depth hypotheses depth_values [D, h + 2 pad, w + 2 pad] of a
+ * stage from the previous stage's depth map -- network/mvs_models.py:536-573 (get_cur_depth_range_samples / get_depth_range_samples) as
+ * CascadeMVSNet.forward strings them together, network/mvs_models.py:693-762: bilinear up-sampling of the depth to the full resolution H x W, a
+ * clamped band around it, D equally spaced samples per pixel, trilinear interpolation down to the stage's h x w (the depth axis keeps its size:
+ * identity), and DepthNet's replicate padding (:598).  One launch; the full-resolution volume of the reference is never stored.
+ *   MAP mode (cur_depth given; stages 2 and 3), every interpolation under torch's align_corners=False rule
+ *   (src = max((dst + 0.5) * n_in / n_out - 0.5, 0), taps floor(src) and min(floor(src) + 1, n_in - 1), weights 1 - l and l):
+ *     c(Y, X)   = bilinear sample of cur_depth [h0, w0] at full-resolution pixel (Y, X)
+ *     mn        = max(c - D / 2 * interval_pixel, near),  mx = min(c + D / 2 * interval_pixel, far),
+ *                 interval_pixel = k * (far - near), or k * interval[0] where the caller holds the interval as a device value of its own
+ *     s_d(Y, X) = mn + d * (mx - mn) / (D - 1)
+ *     out[d, y + pad, x + pad] = bilinear sample of s_d at (y, x) of the h x w grid; the border of `pad` pixels repeats the edge value.
+ *     Sizes: h0 <= H, w0 <= W, h <= H, w <= W (any ratio, integer or not).
+ *   ROW mode (row given; stage 1): mn = row[0], mx = row[D_in - 1], the same s_d for every pixel; H, W, h0, w0, k, near_far, interval are not read.
+ * Exactly one of cur_depth / row is non-NULL.  near and far are read on the device (near_far[0], near_far[1]): no host copy of a device
+ * value on this path.  D >= 2.  An output of zero elements (h + 2 pad == 0 or w + 2 pad == 0) is success, nothing launched.  No backward: the
+ * reference detaches the depth between stages (grad_method="detach", the only mode it builds).
+ * (Declared with a struct tag: the closing line of every typedef above is what tests/test_abi_host.py matches against the v6 struct table of
+ *  uc_nerf_amd/_lib.py, which stays as it was; this struct is mirrored in _lib.ADDED_STRUCTS.) */
+struct ucnerf_depth_hypotheses_params {
+    int32_t D, h, w, pad;      /* output [D, h + 2 pad, w + 2 pad] */
+    int32_t H, W;              /* intermediate (full) resolution; map mode */
+    int32_t h0, w0;            /* size of cur_depth; map mode */
+    int32_t D_in;              /* length of row; row mode */
+    float k;                   /* interval_pixel = k * (far - near); CascadeMVSNet passes depth_interals_ratio[stage] / 48 */
+    const float* cur_depth;    /* [h0, w0] or NULL */
+    const float* row;          /* [D_in] or NULL */
+    const float* near_far;     /* [2] = (near, far); map mode */
+    const float* interval;     /* [1] or NULL (= far - near); map mode */
+    float* out;                /* [D, h + 2 pad, w + 2 pad] */
+};
+typedef struct ucnerf_depth_hypotheses_params ucnerf_depth_hypotheses_params;
+int ucnerf_depth_hypotheses(const ucnerf_depth_hypotheses_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * a10  one fused render pass -- network/renderer.py:215-255 (rendering) with the projection of
  *      utils/utils.py:716-724 in front: rays + depths -> world points -> stage coordinates -> features ->

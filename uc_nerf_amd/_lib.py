@@ -135,6 +135,11 @@ class DepthRegressBwdParams(C.Structure):
     _fields_ = [("fwd", DepthRegressParams), ("g_depth", vp), ("g_confidence", vp), ("g_prob_pre", vp)]
 
 
+class DepthHypothesesParams(C.Structure):
+    _fields_ = [("D", i32), ("h", i32), ("w", i32), ("pad", i32), ("H", i32), ("W", i32), ("h0", i32), ("w0", i32), ("D_in", i32), ("k", f32),
+                ("cur_depth", vp), ("row", vp), ("near_far", vp), ("interval", vp), ("out", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -167,6 +172,10 @@ STRUCTS = {
     "ucnerf_cost_volume_bwd_params": CostVolumeBwdParams, "ucnerf_depth_regress_bwd_params": DepthRegressBwdParams,
     "ucnerf_cl_sources": ClSources, "ucnerf_cl_grads": ClGrads, "ucnerf_build_rays_test_params": BuildRaysTestParams,
 }
+
+# structs added to ABI v6 after its struct table was fixed (STRUCTS above is that table, kept as it was: additive entry points move nothing in it);
+# checked against the library's sizeof() at load time like the others
+ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -226,6 +235,7 @@ SYMBOLS = {
     "ucnerf_depth_regress": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress_bwd": (C.c_int, [_P, _P]),
+    "ucnerf_depth_hypotheses": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),
@@ -261,7 +271,7 @@ def lib():
         fn.restype, fn.argtypes = res, args
     if L.ucnerf_abi_version() != ABI_VERSION:
         raise RuntimeError("uc_nerf_amd: ABI version mismatch")
-    for cname, cls in STRUCTS.items():
+    for cname, cls in list(STRUCTS.items()) + list(ADDED_STRUCTS.items()):
         got = L.ucnerf_sizeof(cname.encode())
         if got != C.sizeof(cls):
             raise RuntimeError("uc_nerf_amd: struct %s is %d bytes in the library, %d in the binding"

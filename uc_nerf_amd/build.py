@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libucnerf_hip.so")
-SOURCES = ["rays.hip", "gather.hip", "gather_cl.hip", "mlp.hip", "mlp_bf16.hip", "mlp_bwd.hip", "mlp_bwd_chain.hip", "mlp_wgrad.hip", "composite.hip", "sample_pdf.hip", "render.hip", "mvs.hip"]
+SOURCES = ["rays.hip", "gather.hip", "gather_cl.hip", "mlp.hip", "mlp_bf16.hip", "mlp_bwd.hip", "mlp_bwd_chain.hip", "mlp_wgrad.hip", "composite.hip", "sample_pdf.hip", "render.hip", "mvs.hip", "cascade.hip"]
 # (source, object name, extra flags): translation units built more than once with different switches
 VARIANTS = [("mlp_bf16.hip", "mlp_bf16_plain.o", ["-DUCNERF_BF16_BUILD_TERMS=1"]), ("mlp_bf16.hip", "mlp_bf16_tail.o", ["-DUCNERF_BF16_BUILD_TAIL=1"]),
             # the same three builds with fp16 terms (ucnerf_mlp_config.operand == 1, ABI v6): entry points under the suffix _h16

@@ -3,8 +3,9 @@
 parameter names/shapes (so reference checkpoints load) and return contracts.  All arithmetic runs in
 libucnerf_hip.so; tensors must live on a ROCm device.
 
-Not mirrored (out of scope): the legacy MVSNet classes below line 289 and CascadeMVSNet itself --
-`create_ucnerf` takes the consistency learner from `args.network_mvs` (any nn.Module) instead of downloading one.
+Not mirrored (out of scope): the legacy MVSNet classes below line 289 and CascadeMVSNet's CNNs (its stage
+loop is mirrored in mvs_models.py) -- `create_ucnerf` takes the consistency learner from `args.network_mvs` (any nn.Module)
+instead of downloading one.
 """
 import torch
 import torch.nn as nn

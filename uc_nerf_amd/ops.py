@@ -1202,6 +1202,45 @@ def depth_regress(prob_pre, depth_values, prob_init=None, pad=0):
     return _DepthRegressFn.apply(prob_pre, depth_values.detach(), prob_init, int(pad))
 
 
+def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=0.0, full_hw=None, pad=0, interval=None):
+    """The depth hypotheses of one cascade stage in one launch (network/mvs_models.py:536-573 as CascadeMVSNet.forward uses them, :693-762):
+    -> depth_values [ndepth, h + 2 pad, w + 2 pad], (h, w) = out_hw, the border of `pad` pixels repeating the edge (DepthNet's replicate pad).
+    Map mode: cur_depth [h0,w0] = the previous stage's depth, near_far a DEVICE tensor (near, far), interval_pixel = k * (far - near) -- or
+    k * interval for a one-element device tensor `interval` --, full_hw the resolution the reference up-samples to before it interpolates back down (default: out_hw).  Row mode: row [D_in], the band
+    row[0] .. row[-1] for every pixel.  No autograd: the inputs are taken detached, as the reference hands them over."""
+    if (cur_depth is None) == (row is None):
+        raise RuntimeError("uc_nerf_amd.depth_hypotheses: exactly one of cur_depth (map mode) and row (row mode)")
+    h, w = int(out_hw[0]), int(out_hw[1])
+    H, W = (h, w) if full_hw is None else (int(full_hw[0]), int(full_hw[1]))
+    p = L.DepthHypothesesParams()
+    p.D, p.h, p.w, p.pad, p.H, p.W, p.k = int(ndepth), h, w, int(pad), H, W, float(k)
+    if cur_depth is not None:
+        cur_depth = _f32(cur_depth.detach(), "cur_depth")
+        if cur_depth.dim() != 2 or near_far is None:
+            raise RuntimeError("uc_nerf_amd.depth_hypotheses: map mode takes cur_depth [h0,w0] and near_far")
+        near_far = _f32(near_far.detach(), "near_far")
+        if near_far.numel() != 2 or near_far.device != cur_depth.device:
+            raise RuntimeError("uc_nerf_amd.depth_hypotheses: near_far must hold (near, far) on cur_depth's device")
+        p.h0, p.w0 = cur_depth.shape
+        p.cur_depth, p.near_far = _ptr(cur_depth), _ptr(near_far)
+        if interval is not None:
+            interval = _f32(interval.detach(), "interval")
+            if interval.numel() != 1 or interval.device != cur_depth.device:
+                raise RuntimeError("uc_nerf_amd.depth_hypotheses: interval must hold one value on cur_depth's device")
+            p.interval = _ptr(interval)
+        dev = cur_depth.device
+    else:
+        row = _f32(row.detach(), "row")
+        if row.dim() != 1:
+            raise RuntimeError("uc_nerf_amd.depth_hypotheses: row mode takes row [D_in]")
+        p.D_in, p.row = row.shape[0], _ptr(row)
+        dev = row.device
+    out = torch.empty(max(p.D, 0), max(h + 2 * p.pad, 0), max(w + 2 * p.pad, 0), device=dev)
+    p.out = _ptr(out)
+    _launch("ucnerf_depth_hypotheses", p, dev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ a10
 class RenderPass:
     """Pre-bound arguments of ucnerf_render_fused_fwd for one scene; call it with (rays_d, z).
