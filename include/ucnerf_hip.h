@@ -181,6 +181,61 @@ typedef struct {
 } ucnerf_build_rays_test_params;
 int ucnerf_build_rays_test(const ucnerf_build_rays_test_params* p, void* stream);
 
+/* a1 + a3 + a4 of the TRAINING step in one launch (added to ABI v6; nothing above moved) -- utils/utils.py:400-597 (build_rays) with the pixel
+ * samplers it calls, :169-215 (get_rays_with_random_patches, confidence picks), :245-247 (get_rays_mvs, uniform pixels) and :304
+ * (get_rays_mvs_coord): R = P ps^2 + n_uniform + n_coord rays, in the reference's order --
+ *   rays 0 .. P/2 ps^2:   patch k = r / ps^2, row-major inside the patch: cell_r = clamp((sel0[k] / W) / ps, 0, H/ps - 2),
+ *                         cell_c = clamp((sel0[k] % W) / ps, 0, W/ps - 2), row = cell_r ps + shift[k][0] + (r % ps^2) / ps,
+ *                         col = cell_c ps + shift[k][1] + (r % ps^2) % ps (the clamp keeps a patch with shifts in [0, ps) inside the image);
+ *   the next P/2 ps^2:    the same with sel1 and shift[P/2 + k];
+ *   the next n_uniform:   (uy[i], ux[i]);
+ *   the last n_coord:     (coords[i][0], coords[i][1]), rows coord_stride floats apart.
+ * Per ray: the direction through the float pixel, the integer pixel by truncation (pix, what .long() gives), the colour imgs[0,0,:,row,col],
+ * and from there what the evaluation builder above does -- the three ranges at (row, col) // (4, 2, 1) with each volume's own row width (a padded
+ * stage-3 volume is indexed without an offset, as the reference does), the sorted and jittered depths, the world points and their four
+ * normalised copies.  Same values as the per-segment ray_gen calls, torch indexing, sample_cascade and ndc_project, bit for bit.  The draws
+ * (torch.multinomial, numpy's shifts, torch.randint, torch.rand) stay the caller's; sel0 / sel1 are what torch.multinomial returns on the device
+ * and are never read back.  Index reads are clamped into the image: a pick, shift or coordinate outside it (the reference raises) cannot
+ * fault, its values are unspecified.  UCNERF_EINVAL: a negative count, odd P, ps < 1, H / ps < 2 or W / ps < 2 with P > 0, S no multiple
+ * of 3 or above 768, a depth_values[k] smaller than the image at its resolution, R S 3 or R 6 beyond int32, a NULL required array.  R = 0
+ * is success, nothing launched; any segment may be empty (its arrays are then not read). */
+struct ucnerf_build_rays_train_params {
+    int32_t S;                 /* samples per ray (multiple of 3, <= 768) */
+    int32_t H, W;
+    int32_t P, ps;             /* patches (even: P/2 from each map), patch edge */
+    int32_t n_uniform, n_coord;
+    int32_t coord_stride;      /* floats between the rows of coords */
+    int32_t dv_d[3], dv_h[3], dv_w[3];   /* sizes of depth_values[k] */
+    int64_t img_stride_c, img_stride_h, img_stride_w;   /* ELEMENT strides of the channel, row and column axes of imgs */
+    const float* K;            /* [3,3] intrinsics of the rendered view (device) */
+    const float* c2w;          /* [>=3,4] camera-to-world of the rendered view (device, rows 4 floats apart) */
+    const float* w2c_ref;      /* [>=3,4] reference view (device) */
+    const float* K_ref;        /* [3,3] (device) */
+    const float* near_far_ref; /* [2] scene range (near, far) (device) */
+    const float* depth_values[3];  /* [D_k,h_k,w_k] hypotheses of cascade stage k + 1 */
+    const float* imgs;         /* element (0, 0, 0) of the image imgs[0,0]: 3 channels x H x W under the strides above */
+    const int64_t* sel0;       /* [P/2] flattened-pixel picks from the confidence map */
+    const int64_t* sel1;       /* [P/2] picks from the uncertainty map */
+    const int32_t* shift;      /* [P,2] (row, col) shift of each patch inside its cell */
+    const float* ux;           /* [n_uniform] columns */
+    const float* uy;           /* [n_uniform] rows */
+    const float* coords;       /* [n_coord,2] (row, col) */
+    const float* t_rand;       /* [R,S] uniform draws, or NULL for no jitter */
+    float* rays_o;             /* [3] out: c2w[:3,3] */
+    float* rays_d;             /* [R,3] out */
+    float* colors;             /* [R,3] out */
+    int64_t* pix;              /* [2,R] out (row, col) */
+    float* near_far;           /* [R,6] out or NULL */
+    float* z;                  /* [R,S] out */
+    float* pts;                /* [R,S,3] out */
+    float* ndc1;               /* [R,S,3] out: stage copies and the scene-normalised copy */
+    float* ndc2;
+    float* ndc3;
+    float* ndc;
+};
+typedef struct ucnerf_build_rays_train_params ucnerf_build_rays_train_params;
+int ucnerf_build_rays_train(const ucnerf_build_rays_train_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * a4  world -> reference-view normalised coordinates -- utils/utils.py:323-373 (get_ndc_coordinate).
  *     p_cam = p R^T + T; |z|<1e-4 -> 1e-4; q = p_cam K^T; xy = q.xy/q.z / inv_scale;

@@ -140,6 +140,15 @@ class DepthHypothesesParams(C.Structure):
                 ("cur_depth", vp), ("row", vp), ("near_far", vp), ("interval", vp), ("out", vp)]
 
 
+class BuildRaysTrainParams(C.Structure):
+    _fields_ = [("S", i32), ("H", i32), ("W", i32), ("P", i32), ("ps", i32), ("n_uniform", i32), ("n_coord", i32), ("coord_stride", i32),
+                ("dv_d", i32 * 3), ("dv_h", i32 * 3), ("dv_w", i32 * 3), ("img_stride_c", C.c_int64), ("img_stride_h", C.c_int64),
+                ("img_stride_w", C.c_int64), ("K", vp), ("c2w", vp), ("w2c_ref", vp), ("K_ref", vp), ("near_far_ref", vp), ("depth_values", vp * 3),
+                ("imgs", vp), ("sel0", vp), ("sel1", vp), ("shift", vp), ("ux", vp), ("uy", vp), ("coords", vp), ("t_rand", vp), ("rays_o", vp),
+                ("rays_d", vp), ("colors", vp), ("pix", vp), ("near_far", vp), ("z", vp), ("pts", vp), ("ndc1", vp), ("ndc2", vp), ("ndc3", vp),
+                ("ndc", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -175,7 +184,7 @@ STRUCTS = {
 
 # structs added to ABI v6 after its struct table was fixed (STRUCTS above is that table, kept as it was: additive entry points move nothing in it);
 # checked against the library's sizeof() at load time like the others
-ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams}
+ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -202,6 +211,7 @@ SYMBOLS = {
     "ucnerf_sample_cascade": (C.c_int, [_P, _P]),
     "ucnerf_ndc_project": (C.c_int, [_P, _P]),
     "ucnerf_build_rays_test": (C.c_int, [_P, _P]),
+    "ucnerf_build_rays_train": (C.c_int, [_P, _P]),
     "ucnerf_embed": (C.c_int, [_P, _P]),
     "ucnerf_feat_gather_fwd": (C.c_int, [_P, _P]),
     "ucnerf_feat_gather_bwd": (C.c_int, [_P, _P]),

@@ -203,17 +203,16 @@ __global__ void __launch_bounds__(64) sample_cascade_kernel(ucnerf_sample_cascad
     }
 }
 
-// ------------------------------------------------------------------------------------------- a1 + a3 + a4 of the evaluation loop, one launch
-// utils/utils.py:600-739 (build_rays_test): one 64-thread block per ray, the arithmetic of ray_gen_one (grid mode), sample_cascade_kernel and
-// ndc_project_kernel in that order on the same values -- bit-identical to the three launches.  Matrices come from device memory (uniform loads).
-__global__ void __launch_bounds__(64) build_rays_test_kernel(ucnerf_build_rays_test_params p) {
-    __shared__ float zs[1024];
-    const int r = blockIdx.x;
+// ------------------------------------------------------------------------------------------- a1 + a3 + a4 of the two ray builders, one launch each
+// utils/utils.py:600-739 (build_rays_test) and :400-597 (build_rays): one 64-thread block per ray, the arithmetic of ray_gen_one (pixel-list mode;
+// grid mode hands in the same floats), sample_cascade_kernel and ndc_project_kernel in that order on the same values -- bit-identical to the three
+// launches.  Matrices come from device memory (uniform loads).  Ray r of the launch looks through the pixel (y, x) = (row, col) as floats; the
+// hypothesis volumes are read at the integer pixel (row, col), which the caller keeps inside the H x W image.  Params: either builder's struct.
+template <class Params>
+__device__ __forceinline__ void cascade_ray(const Params& p, int r, float x, float y, int row, int col, float* zs) {
     const int S = p.S, n3 = S / 3;
-    const int idx = p.grid_start + r;
-    const int row = idx / p.W, col = idx % p.W;
     float wx, wy, wz;
-    pinhole_ray((float)col, (float)row, p.K[0], p.K[2], p.K[4], p.K[5], p.c2w, &wx, &wy, &wz);
+    pinhole_ray(x, y, p.K[0], p.K[2], p.K[4], p.K[5], p.c2w, &wx, &wy, &wz);
     const float ox = p.c2w[3], oy = p.c2w[7], oz = p.c2w[11];
     float nf[6];
 #pragma unroll
@@ -282,6 +281,48 @@ __global__ void __launch_bounds__(64) build_rays_test_kernel(ucnerf_build_rays_t
         p.ndc3[o] = u; p.ndc3[o + 1] = v; p.ndc3[o + 2] = (qz - nf[4]) / (nf[5] - nf[4]);
         p.ndc[o] = u; p.ndc[o + 1] = v; p.ndc[o + 2] = (qz - near) / (far - near);
     }
+}
+
+__global__ void __launch_bounds__(64) build_rays_test_kernel(ucnerf_build_rays_test_params p) {
+    __shared__ float zs[1024];
+    const int idx = p.grid_start + blockIdx.x;
+    const int row = idx / p.W, col = idx % p.W;
+    cascade_ray(p, blockIdx.x, (float)col, (float)row, row, col, zs);
+}
+
+// utils/utils.py:400-597 (build_rays) behind :169-215, :245-247 and :304: the ray's pixel from one of four segments -- the two halves of the
+// patches (multinomial picks -> clamped cell -> shifted ps x ps block, row-major), the uniform pixels, the sparse-depth coordinates.  Index reads
+// are clamped into the image (and with it into the volumes, whose sizes the host checked against the image): a bad pick, shift or coordinate
+// reads a wrong pixel, it cannot fault.
+__global__ void __launch_bounds__(64) build_rays_train_kernel(ucnerf_build_rays_train_params p) {
+    __shared__ float zs[1024];
+    const int r = blockIdx.x;
+    const int pp = p.ps * p.ps, n_patch = p.P * pp;
+    float x, y;
+    if (r < n_patch) {
+        const int k = r / pp, e = r % pp, half = p.P / 2;
+        const long long sel = k < half ? p.sel0[k] : p.sel1[k - half];
+        const long long cell_r = min(max((sel / p.W) / p.ps, 0LL), (long long)(p.H / p.ps - 2));
+        const long long cell_c = min(max((sel % p.W) / p.ps, 0LL), (long long)(p.W / p.ps - 2));
+        y = (float)(cell_r * p.ps + p.shift[2 * k] + e / p.ps);
+        x = (float)(cell_c * p.ps + p.shift[2 * k + 1] + e % p.ps);
+    } else if (r < n_patch + p.n_uniform) {
+        y = p.uy[r - n_patch];
+        x = p.ux[r - n_patch];
+    } else {
+        const float* c = p.coords + (size_t)(r - n_patch - p.n_uniform) * p.coord_stride;
+        y = c[0];
+        x = c[1];
+    }
+    const long long prow = (long long)y, pcol = (long long)x;          // .long(): truncation
+    const int row = (int)min(max(prow, 0LL), (long long)(p.H - 1)), col = (int)min(max(pcol, 0LL), (long long)(p.W - 1));
+    if (threadIdx.x == 0) {
+        p.pix[r] = prow;
+        p.pix[(size_t)(n_patch + p.n_uniform + p.n_coord) + r] = pcol;
+        const float* px = p.imgs + row * p.img_stride_h + col * p.img_stride_w;      // imgs[0, 0, :, row, col]
+        for (int c = 0; c < 3; ++c) p.colors[3 * (size_t)r + c] = px[c * p.img_stride_c];
+    }
+    cascade_ray(p, r, x, y, row, col, zs);
 }
 
 // ------------------------------------------------------------------------------------------- a4
@@ -410,7 +451,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_mlp_config); SZ(ucnerf_mlp_params); SZ(ucnerf_mlp_bwd_params); SZ(ucnerf_composite_params);
     SZ(ucnerf_composite_bwd_params); SZ(ucnerf_sample_pdf_params); SZ(ucnerf_merge_rows_params); SZ(ucnerf_cost_volume_params); SZ(ucnerf_depth_regress_params); SZ(ucnerf_cost_volume_bwd_params); SZ(ucnerf_depth_regress_bwd_params); SZ(ucnerf_render_params);
     SZ(ucnerf_render_bwd_params); SZ(ucnerf_cl_sources); SZ(ucnerf_cl_grads); SZ(ucnerf_build_rays_test_params);
-    SZ(ucnerf_depth_hypotheses_params);
+    SZ(ucnerf_depth_hypotheses_params); SZ(ucnerf_build_rays_train_params);
 #undef SZ
     return -1;
 }
@@ -506,6 +547,38 @@ int ucnerf_build_rays_test(const ucnerf_build_rays_test_params* p, void* stream)
     }
     hipLaunchKernelGGL(build_rays_test_kernel, dim3(p->n), dim3(64), 0, (hipStream_t)stream, *p);
     return check_launch("build_rays_test");
+}
+
+int ucnerf_build_rays_train(const ucnerf_build_rays_train_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "build_rays_train: null params");
+    UCNERF_REQUIRE(p->P >= 0 && p->n_uniform >= 0 && p->n_coord >= 0, "build_rays_train: negative count (P %d, n_uniform %d, n_coord %d)", p->P, p->n_uniform,
+                   p->n_coord);
+    UCNERF_REQUIRE(p->P % 2 == 0, "build_rays_train: P = %d patches (one half per map: even)", p->P);
+    UCNERF_REQUIRE(p->ps >= 1, "build_rays_train: ps = %d", p->ps);
+    UCNERF_REQUIRE(p->P == 0 || (p->H / p->ps >= 2 && p->W / p->ps >= 2), "build_rays_train: a %d x %d image has no two cells of %d pixels each way", p->H, p->W,
+                   p->ps);
+    const long long patch = (long long)p->ps * p->ps;
+    UCNERF_REQUIRE(p->P == 0 || patch <= INT_MAX / 3, "build_rays_train: patches of %d x %d pixels overflow the int indexing of the outputs", p->ps, p->ps);
+    const long long R = p->P * patch + p->n_uniform + p->n_coord;
+    if (R == 0) return UCNERF_OK;
+    UCNERF_REQUIRE(p->S >= 3 && p->S % 3 == 0 && p->S <= 768, "build_rays_train: S = %d (multiple of 3, <= 768)", p->S);
+    UCNERF_REQUIRE(R * p->S * 3 <= INT_MAX && R * 6 <= INT_MAX, "build_rays_train: %lld rays x %d samples overflow the int indexing of the outputs", R, p->S);
+    UCNERF_REQUIRE(p->K && p->c2w && p->w2c_ref && p->K_ref && p->near_far_ref && p->depth_values[0] && p->depth_values[1] && p->depth_values[2] && p->imgs,
+                   "build_rays_train: null input");
+    UCNERF_REQUIRE(p->P == 0 || (p->sel0 && p->sel1 && p->shift), "build_rays_train: patches without sel0 / sel1 / shift (null input)");
+    UCNERF_REQUIRE(p->n_uniform == 0 || (p->ux && p->uy), "build_rays_train: uniform pixels without ux / uy (null input)");
+    UCNERF_REQUIRE(p->n_coord == 0 || p->coords, "build_rays_train: n_coord = %d without coords (null input)", p->n_coord);
+    UCNERF_REQUIRE(p->rays_o && p->rays_d && p->colors && p->pix && p->z && p->pts && p->ndc1 && p->ndc2 && p->ndc3 && p->ndc, "build_rays_train: null output");
+    UCNERF_REQUIRE(p->H >= 2 && p->W >= 2, "build_rays_train: a %d x %d image", p->H, p->W);
+    UCNERF_REQUIRE(p->coord_stride >= 0 && p->img_stride_c >= 0 && p->img_stride_h >= 0 && p->img_stride_w >= 0, "build_rays_train: negative stride");
+    for (int k = 0; k < 3; ++k) {
+        const int div = 4 >> k;
+        UCNERF_REQUIRE(p->dv_d[k] >= 1 && p->dv_h[k] >= (p->H - 1) / div + 1 && p->dv_w[k] >= (p->W - 1) / div + 1,
+                       "build_rays_train: depth_values[%d] is %d x %d x %d, the image needs at least %d x %d", k, p->dv_d[k], p->dv_h[k], p->dv_w[k],
+                       (p->H - 1) / div + 1, (p->W - 1) / div + 1);
+    }
+    hipLaunchKernelGGL(build_rays_train_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, *p);
+    return check_launch("build_rays_train");
 }
 
 int ucnerf_ndc_project(const ucnerf_ndc_project_params* p, void* stream) {

@@ -331,6 +331,90 @@ def build_rays_test(H, W, grid_start, n, S, K, c2w, w2c_ref, K_ref, near_far_ref
     return out
 
 
+def _dev_as(t, name, dtype):
+    """`t` as a contiguous `dtype` tensor on its own device (converted there when it has to be); never uploaded, never read back."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError("uc_nerf_amd: %s must live on a ROCm device" % name)
+    return t if t.dtype == dtype and t.is_contiguous() else t.to(dtype).contiguous()
+
+
+def build_rays_train(imgs, K, c2w, w2c_ref, K_ref, near_far_ref, depth_values, S, patch_size, sel0=None, sel1=None, shift=None, ux=None, uy=None,
+                     coords=None, t_rand=None, want_ranges=False):
+    """The training step's ray builder in ONE launch (utils/utils.py:400-597; ucnerf_build_rays_train) behind the caller's draws: the rays of
+    P patches of patch_size^2 pixels (sel0 / sel1 [P/2] int64, torch.multinomial's picks from the confidence and the uncertainty map as they are on
+    the device; shift [P,2] int32, each patch's (row, col) shift inside its cell), then of the pixels (uy, ux) [n_uniform], then of
+    coords [n_coord,2] (row, col); any segment may be left out.  imgs [N,V,3,H,W] is read at [0,0] under its own strides, depth_values are the
+    three stages' [.., D_k, h_k, w_k]; every matrix is a DEVICE tensor read in place (K [3,3], c2w [4,4] or [3,4], w2c_ref, K_ref, near_far_ref
+    [2]).  Nothing is read back to the host and nothing is uploaded.
+    -> dict(rays_o [3], rays_d [R,3], colors [R,3], pix [2,R] int64 (row, col), z [R,S], pts / stage1 / stage2 / stage3 / ndc [R,S,3]
+    (+ ranges [R,6])); the five coordinate arrays are one allocation."""
+    if not (torch.is_tensor(imgs) and imgs.is_cuda):
+        raise RuntimeError("uc_nerf_amd: imgs must live on a ROCm device")
+    if imgs.dim() != 5 or imgs.shape[2] != 3 or imgs.dtype != torch.float32:
+        raise RuntimeError("uc_nerf_amd.build_rays_train: imgs must be float32 [N,V,3,H,W], got %s %s" % (imgs.dtype, tuple(imgs.shape)))
+    dev = imgs.device
+    f32, S = torch.float32, int(S)
+    K_, c2w_, w2c_, Kr_ = _dev_as(K, "K", f32), _dev_as(c2w, "c2w", f32), _dev_as(w2c_ref, "w2c_ref", f32), _dev_as(K_ref, "K_ref", f32)
+    nf_ = _dev_as(near_far_ref, "near_far_ref", f32)
+    if K_.numel() < 9 or Kr_.numel() < 9 or nf_.numel() < 2 or c2w_.numel() < 12 or w2c_.numel() < 12 or c2w_.shape[-1] != 4 or w2c_.shape[-1] != 4:
+        raise RuntimeError("uc_nerf_amd.build_rays_train: K / K_ref must be [3,3], c2w / w2c_ref [3,4] or [4,4], near_far_ref [2]")
+    p = L.BuildRaysTrainParams()
+    p.S, p.H, p.W, p.ps = S, imgs.shape[3], imgs.shape[4], int(patch_size)
+    p.imgs = imgs.data_ptr()                                             # element [0,0,0,0,0]
+    p.img_stride_c, p.img_stride_h, p.img_stride_w = imgs.stride(2), imgs.stride(3), imgs.stride(4)
+    keep = [K_, c2w_, w2c_, Kr_, nf_]
+    for k, dv in enumerate(depth_values):
+        dv = _dev_as(dv, "depth_values", f32)
+        keep.append(dv)
+        if dv.dim() < 3 or dv.numel() != dv.shape[-3] * dv.shape[-2] * dv.shape[-1]:
+            raise RuntimeError("uc_nerf_amd.build_rays_train: depth_values must be [1,D,h,w] (one batch entry)")
+        p.dv_d[k], p.dv_h[k], p.dv_w[k] = dv.shape[-3], dv.shape[-2], dv.shape[-1]
+        p.depth_values[k] = dv.data_ptr()
+    p.K, p.c2w, p.w2c_ref, p.K_ref, p.near_far_ref = K_.data_ptr(), c2w_.data_ptr(), w2c_.data_ptr(), Kr_.data_ptr(), nf_.data_ptr()
+    if (sel0 is None) != (sel1 is None) or (sel0 is None) != (shift is None):
+        raise RuntimeError("uc_nerf_amd.build_rays_train: sel0, sel1 and shift come together")
+    if sel0 is not None:
+        sel0, sel1, shift = _dev_as(sel0, "sel0", torch.int64), _dev_as(sel1, "sel1", torch.int64), _dev_as(shift, "shift", torch.int32)
+        if sel0.numel() != sel1.numel() or shift.numel() != 4 * sel0.numel():
+            raise RuntimeError("uc_nerf_amd.build_rays_train: sel0 / sel1 must be [P/2] and shift [P,2]")
+        p.P, p.sel0, p.sel1, p.shift = 2 * sel0.numel(), sel0.data_ptr(), sel1.data_ptr(), shift.data_ptr()
+    if (ux is None) != (uy is None):
+        raise RuntimeError("uc_nerf_amd.build_rays_train: ux and uy come together")
+    if ux is not None:
+        ux, uy = _dev_as(ux, "ux", f32), _dev_as(uy, "uy", f32)
+        if ux.numel() != uy.numel():
+            raise RuntimeError("uc_nerf_amd.build_rays_train: ux and uy must have the same length")
+        p.n_uniform, p.ux, p.uy = ux.numel(), ux.data_ptr(), uy.data_ptr()
+    if coords is not None:
+        if not (torch.is_tensor(coords) and coords.is_cuda):
+            raise RuntimeError("uc_nerf_amd: coords must live on a ROCm device")
+        if coords.dim() != 2 or coords.shape[1] < 2:
+            raise RuntimeError("uc_nerf_amd.build_rays_train: coords must be [n,2] (row, col)")
+        if coords.dtype != f32 or (coords.shape[0] > 0 and coords.stride(1) != 1):
+            coords = coords.float().contiguous()
+        p.n_coord, p.coords, p.coord_stride = coords.shape[0], coords.data_ptr(), coords.stride(0)
+    n = p.P * p.ps * p.ps + p.n_uniform + p.n_coord
+    m = n * S
+    if t_rand is not None:
+        t_rand = _dev_as(t_rand, "t_rand", f32)
+        if t_rand.numel() != m:
+            raise RuntimeError("uc_nerf_amd.build_rays_train: t_rand must be [R,S] = [%d,%d]" % (n, S))
+    buf = torch.empty(5, n, S, 3, device=dev)                          # pts, stage1, stage2, stage3, ndc: one allocation, five views from one call
+    pts, s1, s2, s3, ndc = buf.unbind(0)
+    z, rays_d, rays_o, colors = torch.empty(n, S, device=dev), torch.empty(n, 3, device=dev), torch.empty(3, device=dev), torch.empty(n, 3, device=dev)
+    pix = torch.empty(2, n, dtype=torch.int64, device=dev)
+    ranges = torch.empty(n, 6, device=dev) if want_ranges else None
+    p.t_rand, p.rays_o, p.rays_d, p.colors, p.pix = _ptr(t_rand), rays_o.data_ptr(), rays_d.data_ptr(), colors.data_ptr(), pix.data_ptr()
+    p.near_far, p.z = _ptr(ranges), z.data_ptr()
+    base, step = buf.data_ptr(), 12 * m
+    p.pts, p.ndc1, p.ndc2, p.ndc3, p.ndc = base, base + step, base + 2 * step, base + 3 * step, base + 4 * step
+    _launch("ucnerf_build_rays_train", p, dev)
+    out = {"rays_o": rays_o, "rays_d": rays_d, "colors": colors, "pix": pix, "z": z, "pts": pts, "stage1": s1, "stage2": s2, "stage3": s3, "ndc": ndc}
+    if want_ranges:
+        out["ranges"] = ranges
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ a5
 def embed(x, n_freqs, layout=0):
     x = _f32(x, "x")

@@ -8,6 +8,8 @@ builders (`build_rays`, `build_rays_test`), the two halves of the feature gather
 Random pixel selection (randint / multinomial / numpy shifts) stays host-side torch/numpy logic exactly where the
 reference has it, in the same call order; everything per-ray or per-sample after that is a HIP kernel.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -46,6 +48,13 @@ def _rays_from_pixels(xs, ys, intrinsic, c2w):
     return rays_o, rays_d, torch.stack((ys.float(), xs.float()))    # pixel_coordinates = (row, col)
 
 
+def _uniform_pixels(H, W, N, is_precrop_iters):
+    """utils/utils.py:239-247: the uniform pixel draws of get_rays_mvs, columns first (host tensors, as the reference draws them)."""
+    if is_precrop_iters and torch.rand((1,)) > 0.3:
+        return torch.randint(W // 6, W - W // 6, (N,)), torch.randint(H // 6, H - H // 6, (N,))
+    return torch.randint(0, W, (N,)), torch.randint(0, H, (N,))
+
+
 def get_rays_mvs(H, W, intrinsic, c2w, N=1024, isRandom=True, is_precrop_iters=False, chunk=-1, idx=-1,
                  with_mask=False, photo_confidence=None):
     """utils/utils.py:217-271 -> (rays_o [3], rays_d [N,3], pixel_coordinates [2,N] as (row, col))."""
@@ -58,12 +67,9 @@ def get_rays_mvs(H, W, intrinsic, c2w, N=1024, isRandom=True, is_precrop_iters=F
     if with_mask:
         select = torch.multinomial(photo_confidence.reshape(-1), N)
         xs, ys = (select % W).float().to(device), (select // W).float().to(device)
-    elif is_precrop_iters and torch.rand((1,)) > 0.3:
-        xs = torch.randint(W // 6, W - W // 6, (N,)).float().to(device)
-        ys = torch.randint(H // 6, H - H // 6, (N,)).float().to(device)
     else:
-        xs = torch.randint(0, W, (N,)).float().to(device)
-        ys = torch.randint(0, H, (N,)).float().to(device)
+        xs, ys = _uniform_pixels(H, W, N, is_precrop_iters)
+        xs, ys = xs.float().to(device), ys.float().to(device)
     return _rays_from_pixels(xs, ys, intrinsic, c2w)
 
 
@@ -175,6 +181,26 @@ def build_rays_test(H, W, tgt_to_world, world_to_ref, intrinsic, near_fars_ref, 
     return o["pts"], o["rays_d"], ndc, o["z"], o["rays_o"].reshape(1, 3).expand(n, -1), ndc_parameters
 
 
+# build_rays: one launch behind the draws (True) or the composition of the per-segment ray_gen calls, torch indexing, sample_cascade and ndc_project
+# (False).  UCNERF_BUILD_RAYS_FUSED=0 / 1 in the environment decides at import, set_build_rays_fused() at run time.
+# Off by default: profiles/build_rays_train.md.
+_BUILD_RAYS_FUSED = os.environ.get("UCNERF_BUILD_RAYS_FUSED", "0") != "0"
+
+
+def set_build_rays_fused(on):
+    """Switches build_rays between its one-launch route and the composed one; returns the previous setting."""
+    global _BUILD_RAYS_FUSED
+    prev, _BUILD_RAYS_FUSED = _BUILD_RAYS_FUSED, bool(on)
+    return prev
+
+
+def _fused_takes(args, imgs, N_samples):
+    """What ucnerf_build_rays_train takes; build_rays goes the composed way with anything else."""
+    ps = int(args.patch_size)
+    return (imgs.is_cuda and imgs.dtype == torch.float32 and imgs.shape[2] == 3 and ps >= 1 and imgs.shape[3] // ps >= 2 and imgs.shape[4] // ps >= 2
+            and N_samples >= 3 and N_samples % 3 == 0 and N_samples <= 768)
+
+
 def build_rays(args, imgs, mvs_confidence, sparse_depths, coords, pose_ref, w2cs, c2ws, intrinsics, N_rays, N_samples,
                pad=0, is_precrop_iters=False, ref_idx=0, with_depth=False, outputs=None):
     """utils/utils.py:400-597, the training sampler: patch_num/2 patches drawn from the confidence map, patch_num/2
@@ -183,6 +209,42 @@ def build_rays(args, imgs, mvs_confidence, sparse_depths, coords, pose_ref, w2cs
     if not with_depth:
         raise UnboundLocalError("build_rays(with_depth=False) leaves depth_candidate undefined in the reference "
                                 "(utils/utils.py:572); train.py always passes with_depth=True")
+    if _BUILD_RAYS_FUSED and _fused_takes(args, imgs, N_samples):
+        return _build_rays_fused(args, imgs, mvs_confidence, coords, pose_ref, c2ws, intrinsics, N_rays, N_samples, pad, is_precrop_iters, ref_idx,
+                                 outputs)
+    return _build_rays_composed(args, imgs, mvs_confidence, sparse_depths, coords, pose_ref, c2ws, intrinsics, N_rays, N_samples, pad,
+                                is_precrop_iters, ref_idx, outputs)
+
+
+def _build_rays_fused(args, imgs, mvs_confidence, coords, pose_ref, c2ws, intrinsics, N_rays, N_samples, pad, is_precrop_iters, ref_idx, outputs):
+    """The reference's draws through its own primitives, in its order and with its shapes (per half torch.multinomial, then numpy's shift pairs patch
+    by patch; the uniform columns, the uniform rows; the jitter), then ONE launch (ucnerf_build_rays_train).  The picks stay on the device; the
+    host-drawn shifts and uniform pixels go up as one small tensor each."""
+    device = imgs.device
+    H, W = imgs.shape[-2:]
+    ps, half = int(args.patch_size), args.patch_num // 2
+    sel, shifts = [], []
+    for confidence in (mvs_confidence, 1 - mvs_confidence):
+        sel.append(torch.multinomial(confidence.reshape(-1), half).to(device))
+        shifts += [np.random.randint(0, ps) for _ in range(2 * half)]                 # (row shift, col shift) per patch
+    xs, ys = _uniform_pixels(H, W, N_rays - 2 * half * ps * ps, is_precrop_iters)
+    uniform = torch.stack((xs, ys)).float().to(device)
+    shift = torch.tensor(shifts, dtype=torch.int32).reshape(-1, 2).to(device)
+    n = 2 * half * ps * ps + xs.numel() + coords.shape[0]
+    t_rand = torch.rand((n, N_samples), device=device)
+    w2c_ref, intrinsic_ref, near_far_ref = pose_ref['w2cs'][ref_idx], pose_ref['intrinsics'][ref_idx], pose_ref['near_fars'][ref_idx]
+    o = ops.build_rays_train(imgs, intrinsics[0], c2ws[0], w2c_ref, intrinsic_ref, near_far_ref,
+                             [outputs["stage%d" % k]['depth_values'] for k in (1, 2, 3)], N_samples, ps, sel[0], sel[1], shift,
+                             uniform[0], uniform[1], coords.to(device), t_rand)
+    ndc = {"stage1": o["stage1"], "stage2": o["stage2"], "stage3": o["stage3"], "ndc": o["ndc"]}
+    ndc_parameters = {'w2c_ref': w2c_ref, 'intrinsic_ref': intrinsic_ref, 'inv_scale': _inv_scale(W, H, device), 'near': near_far_ref[0],
+                      'far': near_far_ref[1], 'pad': pad}
+    return o["pts"], o["rays_d"], o["colors"], ndc, o["z"], o["rays_o"].reshape(1, 3).expand(n, -1), None, ndc_parameters, o["pix"]
+
+
+def _build_rays_composed(args, imgs, mvs_confidence, sparse_depths, coords, pose_ref, c2ws, intrinsics, N_rays, N_samples, pad, is_precrop_iters,
+                         ref_idx, outputs):
+    """The same from the public pixel samplers: a ray_gen launch per segment, torch indexing, sample_cascade, ndc_project."""
     device = imgs.device
     N, V, C, H, W = imgs.shape
     w2c_ref, intrinsic_ref = pose_ref['w2cs'][ref_idx], pose_ref['intrinsics'][ref_idx]
