@@ -12,13 +12,24 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 OBJ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "uc_nerf_amd", "csrc", "_obj")
 
 
-def kernels(obj):
+def unbundle(obj, co):
+    """the gfx950 code object of an object file of the library build -> file `co`; False: the object holds no device code"""
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "a.fatbin"), os.path.join(d, "a.co")
+        fat = os.path.join(d, "a.fatbin")
         subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat], check=True)
+        if os.path.getsize(fat) == 0:
+            return False
         ids = subprocess.run([LLVM + "/clang-offload-bundler", "--list", "--type=o", "--input=" + fat], capture_output=True, text=True, check=True).stdout.split()
         tgt = next(t for t in ids if "gfx950" in t)
         subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--targets=" + tgt, "--input=" + fat, "--output=" + co], check=True)
+    return True
+
+
+def kernels(obj):
+    with tempfile.TemporaryDirectory() as d:
+        co = os.path.join(d, "a.co")
+        if not unbundle(obj, co):
+            return []
         notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     out = []
     for k in re.split(r"\n\s+- \.agpr_count", notes)[1:]:

@@ -41,7 +41,7 @@ struct Mat33 { float m[9]; };
 int device_cus();   // of the CURRENT device, cached per device (thread-safe)
 
 // The status / condition word of the guarded split (ucnerf_*_guarded, ucnerf_*_if): a property of the CALL, not of ucnerf_mlp_config, so it
-// travels beside the parameter structs -- the entry point sets it for the calling thread (SplitGuardScope), the launchers of mlp_bf16.hip read it.
+// travels beside the parameter structs -- the entry point sets it for the calling thread (SplitGuardScope), the launchers of mlp_bf16_host.hip read it.
 //   GUARD_DETECT: fp16 terms with range detection, `word` = the status word the kernels OR into;
 //   GUARD_RUN_IF: `word` = the condition word; a kernel whose word reads zero does nothing.
 enum { GUARD_NONE = 0, GUARD_DETECT = 1, GUARD_RUN_IF = 2 };

@@ -6,6 +6,7 @@
 // A 256-thread block = 4 independent waves; the grid is persistent (waves stride over tiles).
 #include "common.h"
 #include "mlp_layout.h"
+#include "mlp_bf16.h"
 #include "p24.h"
 #include "sincos_cw.h"
 #include "mfma_split.h"
@@ -613,15 +614,6 @@ int launch_mlp_fwd(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t
 #undef LAUNCH
     return check_launch("mlp_fwd");
 }
-
-// mlp_bf16.hip
-int build_pack_index_bf16(const ucnerf_mlp_config* cfg, int32_t* idx);
-int64_t bf16_index_count(const ucnerf_mlp_config* cfg);
-int64_t bf16_stream_floats(const ucnerf_mlp_config* cfg);
-int launch_pack_bf16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st);
-int launch_pack_bf16_tab(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st);
-int launch_mlp_fwd_bf16x3(const ucnerf_mlp_params* p, hipStream_t st);      // mlp_bf16.hip built with TERMS = 3
-int launch_mlp_fwd_bf16_plain(const ucnerf_mlp_params* p, hipStream_t st);   // ... and with TERMS = 1
 
 SplitGuard& split_guard() {
     static thread_local SplitGuard g = {GUARD_NONE, nullptr};

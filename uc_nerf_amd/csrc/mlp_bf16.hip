@@ -29,8 +29,7 @@
 //     less data movement per tile, not more overlap.)
 //   * FUSED instantiation: the tile loop opens with the tile's feature gather -- the operands of the
 //     two bias nets come straight from the channel-last sources instead of a feature buffer written by feat_gather_cl_kernel.
-#include "common.h"
-#include "mlp_layout.h"
+#include "mlp_bf16.h"
 #include "sincos_cw.h"
 #include "gather_cl_device.h"
 #include "raygen_device.h"
@@ -39,25 +38,23 @@
 #include "sample_pdf_device.h"
 #include "mfma_split.h"
 
-#include <cstdlib>
-#include <vector>
-
-// This file is compiled twice (uc_nerf_amd/build.py): UCNERF_BF16_BUILD_TERMS = 3 gives the split-bf16 launcher
-// (launch_mlp_fwd_bf16x3) plus the host-side packing shared by both precisions, = 1 the plain-bf16 launcher only.
+// uc_nerf_amd/build.py compiles this file nine times.  A build holds device code and the table that names it (Bf16Build, mlp_bf16.h: at the end of
+// this file) -- the launchers and everything else on the host side are mlp_bf16_host.hip's.  UCNERF_BF16_BUILD_TERMS = 3 gives the split-bf16 kernels
+// and the packers of the weight stream, which both precisions read, = 1 the plain-bf16 kernels only.
 #ifndef UCNERF_BF16_BUILD_TERMS
 #define UCNERF_BF16_BUILD_TERMS 3
 #endif
-// A third build (-DUCNERF_BF16_BUILD_TAIL=1, TERMS = 3) holds nothing but the TAIL instantiations of the gather-fused kernel and their launcher
-// (launch_fused_tail): the launch that also composites and re-samples the rays of a small pass -- compiled beside the main object, not after it.
+// A third build (-DUCNERF_BF16_BUILD_TAIL=1, TERMS = 3) holds nothing but the TAIL instantiations of the gather-fused kernel: the launch that also
+// composites and re-samples the rays of a small pass -- compiled beside the main object, not after it.
 #ifndef UCNERF_BF16_BUILD_TAIL
 #define UCNERF_BF16_BUILD_TAIL 0
 #endif
 
 namespace ucnerf {
 
-// ucnerf_mlp_config.operand (ABI v6): every build of this file exists twice -- with bf16 terms (UCNERF_OPERAND_FP16 = 0: the entry points below) and with
-// fp16 terms (UCNERF_OPERAND_FP16 = 1: 11-bit hi and lo terms, v_mfma_f32_32x32x16_f16; the same entry points under the suffix _h16, which the
-// bf16 build's entry points forward to when cfg.operand == 1).  These kernels do not watch fp16's range (values beyond 65 504 overflow); the UCNERF_SPLIT_GUARD builds below do.
+// ucnerf_mlp_config.operand (ABI v6): every build of this file exists with bf16 terms (UCNERF_OPERAND_FP16 = 0) and with fp16 terms
+// (UCNERF_OPERAND_FP16 = 1: 11-bit hi and lo terms, v_mfma_f32_32x32x16_f16; its table under the suffix _h16).  These kernels do not watch fp16's
+// range (values beyond 65 504 overflow); the UCNERF_SPLIT_GUARD builds below do.
 #ifndef UCNERF_OPERAND_FP16
 #define UCNERF_OPERAND_FP16 0
 #endif
@@ -72,38 +69,27 @@ namespace ucnerf {
 #if UCNERF_SPLIT_GUARD && !UCNERF_OPERAND_FP16
 #error "UCNERF_SPLIT_GUARD goes with UCNERF_OPERAND_FP16: bf16 terms have float32's range"
 #endif
-#if UCNERF_OPERAND_FP16
+// What a build defines under a name of its own: the table it exports, and the kernels -- a template's instantiations are weak symbols: the linker
+// would keep ONE of two equally named ones and both operand kinds would run the same code.
 #if UCNERF_SPLIT_GUARD
 #define UCNERF_SFX(name) name##_g16
-#else
-#define UCNERF_SFX(name) name##_h16
-#endif
-#define build_pack_index_bf16 UCNERF_SFX(build_pack_index_bf16)
-#define launch_fused_tail UCNERF_SFX(launch_fused_tail)
-#define build_flags_mlp_bf16x3 UCNERF_SFX(build_flags_mlp_bf16x3)
-#define build_flags_mlp_bf16_plain UCNERF_SFX(build_flags_mlp_bf16_plain)
-#define launch_mlp_fwd_bf16x3 UCNERF_SFX(launch_mlp_fwd_bf16x3)
-#define launch_mlp_fwd_bf16x3_save UCNERF_SFX(launch_mlp_fwd_bf16x3_save)
-#define launch_mlp_fwd_bf16x3_gather UCNERF_SFX(launch_mlp_fwd_bf16x3_gather)
-#define launch_mlp_fwd_bf16_plain UCNERF_SFX(launch_mlp_fwd_bf16_plain)
-#define bf16_index_count UCNERF_SFX(bf16_index_count)
-#define bf16_stream_floats UCNERF_SFX(bf16_stream_floats)
-#define launch_pack_bf16 UCNERF_SFX(launch_pack_bf16)
-#define launch_pack_bf16_tab UCNERF_SFX(launch_pack_bf16_tab)
-#if UCNERF_SPLIT_GUARD
 #define mlp_fwd_bf16_kernel mlp_fwd_g16_kernel
 #define pack_all_flat_kernel pack_all_flat_g16_kernel
 #define pack_all_tab_kernel pack_all_tab_g16_kernel
-#else
-#define mlp_fwd_bf16_kernel mlp_fwd_h16_kernel                      // (the kernels too: a template's instantiations are weak symbols -- the linker would keep ONE of two
-#define pack_all_flat_kernel pack_all_flat_h16_kernel                //  equally named ones and both operand kinds would run the same code)
+#elif UCNERF_OPERAND_FP16
+#define UCNERF_SFX(name) name##_h16
+#define mlp_fwd_bf16_kernel mlp_fwd_h16_kernel
+#define pack_all_flat_kernel pack_all_flat_h16_kernel
 #define pack_all_tab_kernel pack_all_tab_h16_kernel
-#endif
-#define UCNERF_OPERAND_DISPATCH(cfg_operand, fn, ...)
 #else
-// (the fp16 builds' entry points: `fn` with this entry point's own arguments, under _g16 when the calling entry point is a guarded one)
-#define UCNERF_OPERAND_DISPATCH(cfg_operand, fn, ...) \
-    do { if ((cfg_operand) == 1) return split_guard().mode == GUARD_DETECT ? fn##_g16(__VA_ARGS__) : fn##_h16(__VA_ARGS__); } while (0)
+#define UCNERF_SFX(name) name
+#endif
+#if UCNERF_BF16_BUILD_TAIL
+#define bf16_build UCNERF_SFX(bf16_build_tail)
+#elif UCNERF_BF16_BUILD_TERMS == 3
+#define bf16_build UCNERF_SFX(bf16_build_x3)
+#else
+#define bf16_build UCNERF_SFX(bf16_build_plain)
 #endif
 #if UCNERF_OPERAND_FP16
 typedef _Float16 op16;
@@ -130,7 +116,6 @@ typedef op16 op16x8 __attribute__((ext_vector_type(8)));      // an operand frag
                                //    per tile of two 4-wave blocks; measured -3.3 % on the launch (profiles/r02_mlp_bf16_experiments.md)
 #endif
 constexpr int BW = UCNERF_BF16_BW;    // waves per block sharing one weight ring: 4 (one per SIMD, two blocks per CU) or 8 (two per SIMD, one block per CU)
-constexpr int SLOT_BYTES = 8192;      // two half-steps: [2][hi0, lo0, hi1, lo1][64 lanes][16 B]
 constexpr int HALF_BYTES = 4096;
 #ifndef UCNERF_BF16_NBUF
 #define UCNERF_BF16_NBUF 4
@@ -138,123 +123,6 @@ constexpr int HALF_BYTES = 4096;
 constexpr int NBUF = UCNERF_BF16_NBUF;   // LDS ring slots (power of two); the slot of ring position g is refilled with position g + NBUF
 constexpr int fused_ring_slots(bool fused, int n_src) { return fused && n_src > 6 && NBUF > 2 ? 2 : NBUF; }      // (see the kernel)
 constexpr int DMA_PER_SLOT = SLOT_BYTES / 1024 / BW;      // 1-KB global_load_lds pieces per wave per slot
-constexpr int KS16_PE_PTS = 4, KS16_PE_DIR = 2, KS16_HID = 8;
-
-struct Bf16Layout {
-    int v, F, kd16, kc16, slots;      // slots = k16-steps per tile (two half-steps each)
-    int64_t const_off_bytes, total_bytes;
-};
-
-static bool bf16_layout(int v, Bf16Layout* B) {
-    if (v < 1 || v > 8) return false;
-    B->v = v; B->F = 24 + 12 * v + 1;
-    B->kd16 = (24 + 4 * v + 15) / 16; B->kc16 = (8 * v + 15) / 16;
-    B->slots = B->kd16 + KS16_PE_PTS + 4 * KS16_HID + (KS16_PE_PTS + KS16_HID) + B->kc16 + KS16_HID + (KS16_HID + KS16_PE_DIR);
-    B->const_off_bytes = (int64_t)B->slots * SLOT_BYTES;
-    B->total_bytes = B->const_off_bytes + (int64_t)CONST_FLOATS * 4;
-    return true;
-}
-
-#if UCNERF_BF16_BUILD_TERMS == 3 && !UCNERF_BF16_BUILD_TAIL
-// ------------------------------------------------------------------------------------------------ host: pack index
-// idx16[e] for every bf16 element e of the stream: flat parameter index | (part << 30) (part 0 = hi, 1 = lo), -1 = zero.
-// Half-steps appear in the order the kernel consumes them (see the schedule in mlp_fwd_bf16_kernel):
-//   bd: step-major (q: pair 0, pair 1) | L0: pair-split | L1..L4: pair-split | L5: pair-split over [h 0..3 | pe 0..3 | h 4..7]
-//   bc: step-major | ft: pair-split | vc: pair-split over [h 0..7 | dir 0..1]
-int build_pack_index_bf16(const ucnerf_mlp_config* cfg, int32_t* idx) {
-    Bf16Layout B;
-    MlpLayout L;
-    if (!bf16_layout(cfg->n_src, &B) || !mlp_layout(cfg->n_src, &L)) return -1;
-    const int v = B.v, W = MLP_W;
-    const int64_t n16 = (int64_t)B.slots * (SLOT_BYTES / 2);
-    for (int64_t i = 0; i < n16 + CONST_FLOATS; ++i) idx[i] = -1;
-    int64_t hidx = 0;
-    auto put_half = [&](const std::vector<int64_t>& row_base, const int (&col)[2][8], int pair) {
-        for (int t = 0; t < 2; ++t)
-            for (int part = 0; part < 2; ++part)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int c = col[lane >> 5][j];
-                        const int64_t e = (((hidx * 4 + t * 2 + part) * 64) + lane) * 8 + j;
-                        idx[e] = c < 0 ? -1 : (int32_t)((row_base[32 * (2 * pair + t) + (lane & 31)] + c) | ((int64_t)part << 30));
-                    }
-        ++hidx;
-    };
-    auto rows = [&](int64_t base, int K) { std::vector<int64_t> rb(128); for (int n = 0; n < 128; ++n) rb[n] = base + (int64_t)n * K; return rb; };
-    auto nat = [&](int q, int K, int (&col)[2][8]) { for (int hh = 0; hh < 2; ++hh) for (int j = 0; j < 8; ++j) { int f = 16 * q + 8 * hh + j; col[hh][j] = f < K ? f : -1; } };
-    auto hid = [&](int q, int base, int (&col)[2][8]) { for (int hh = 0; hh < 2; ++hh) for (int j = 0; j < 8; ++j) col[hh][j] = base + hid_feature16(q >> 1, q & 1, j, hh); };
-    auto pe = [&](int q, int nf, int base, int (&col)[2][8]) {
-        for (int hh = 0; hh < 2; ++hh)
-            for (int j = 0; j < 8; ++j) {
-                int kind, a;
-                pe_slot(8 * q + j, hh, nf, &kind, &a);
-                const int c = pe_column(kind, a, nf, cfg->pe_layout);
-                col[hh][j] = c < 0 ? -1 : base + c;
-            }
-    };
-    // precision 3 (the gather runs inside the kernel, fused_operands below): the two bias nets take their operands in the order the
-    // lane halves produce them -- bd: [stage 1 | stage 2], [stage 3 ch 0..3, view 0 | ch 4..7, view 1], then two views per half and
-    // step (even views in half 0, odd views in half 1); bc: the image features of view 2q + hh in step q
-    const bool fused = cfg->precision == 3;
-    auto bd_fused = [&](int q, int (&col)[2][8]) {
-        for (int hh = 0; hh < 2; ++hh)
-            for (int j = 0; j < 8; ++j) {
-                int c = -1;
-                if (q == 0) c = 8 * hh + j;
-                else if (q == 1 && j < 4) c = 16 + 4 * hh + j;
-                else {
-                    const int pair = q == 1 ? 0 : 1 + 2 * (q - 2) + (j >> 2), view = 2 * pair + hh;
-                    if (view < v) c = 24 + 4 * view + (j & 3);
-                }
-                col[hh][j] = c;
-            }
-    };
-    auto bc_fused = [&](int q, int (&col)[2][8]) {
-        for (int hh = 0; hh < 2; ++hh)
-            for (int j = 0; j < 8; ++j) col[hh][j] = 2 * q + hh < v ? 8 * (2 * q + hh) + j : -1;
-    };
-    int col[2][8];
-    {   // bd, step-major
-        const auto rb = rows(L.p_bdw, 24 + 4 * v);
-        for (int q = 0; q < B.kd16; ++q) { if (fused) bd_fused(q, col); else nat(q, 24 + 4 * v, col); put_half(rb, col, 0); put_half(rb, col, 1); }
-    }
-    {   // L0
-        const auto rb = rows(L.p_lw[0], MLP_PE_PTS);
-        for (int p = 0; p < 2; ++p) for (int q = 0; q < KS16_PE_PTS; ++q) { pe(q, 10, 0, col); put_half(rb, col, p); }
-    }
-    for (int l = 1; l < 5; ++l) {
-        const auto rb = rows(L.p_lw[l], W);
-        for (int p = 0; p < 2; ++p) for (int q = 0; q < KS16_HID; ++q) { hid(q, 0, col); put_half(rb, col, p); }
-    }
-    {   // L5 on [pe | h]: k order h 0..3, pe 0..3, h 4..7
-        const auto rb = rows(L.p_lw[5], W + MLP_PE_PTS);
-        for (int p = 0; p < 2; ++p) {
-            for (int q = 0; q < 4; ++q) { hid(q, MLP_PE_PTS, col); put_half(rb, col, p); }
-            for (int q = 0; q < KS16_PE_PTS; ++q) { pe(q, 10, 0, col); put_half(rb, col, p); }
-            for (int q = 4; q < 8; ++q) { hid(q, MLP_PE_PTS, col); put_half(rb, col, p); }
-        }
-    }
-    {   // bc, step-major
-        const auto rb = rows(L.p_bcw, 8 * v);
-        for (int q = 0; q < B.kc16; ++q) { if (fused) bc_fused(q, col); else nat(q, 8 * v, col); put_half(rb, col, 0); put_half(rb, col, 1); }
-    }
-    {   // feature_linear
-        const auto rb = rows(L.p_fw, W);
-        for (int p = 0; p < 2; ++p) for (int q = 0; q < KS16_HID; ++q) { hid(q, 0, col); put_half(rb, col, p); }
-    }
-    {   // views_linears | view_confi_linears on [feature | dir encoding]: k order h 0..7, dir 0..1
-        std::vector<int64_t> rb(128);
-        for (int n = 0; n < 64; ++n) { rb[n] = L.p_vw + (int64_t)n * (W + MLP_PE_DIR); rb[64 + n] = L.p_vcw + (int64_t)n * (W + MLP_PE_DIR); }
-        for (int p = 0; p < 2; ++p) {
-            for (int q = 0; q < KS16_HID; ++q) { hid(q, 0, col); put_half(rb, col, p); }
-            for (int q = 0; q < KS16_PE_DIR; ++q) { pe(q, 4, W, col); put_half(rb, col, p); }
-        }
-    }
-    return hidx == 2 * (int64_t)B.slots ? 0 : -1;
-}
-
-
-#endif   // UCNERF_BF16_BUILD_TERMS == 3 (host-side packing)
 
 // ------------------------------------------------------------------------------------------------ device helpers
 typedef HiLo<op16x8> Frag;
@@ -379,10 +247,6 @@ __device__ __forceinline__ Frag frag_of(GMax& gmax, const f32x16& a, const f32x1
     return f;
 }
 
-struct BGeom {
-    int F, kd16, kc16, f_img, slots, feat_stride;
-    int const_off_bytes;
-};
 
 // A fragments of one half-step (row-tile pair)
 typedef PairFrags<op16x8> AF;
@@ -534,65 +398,6 @@ __device__ __forceinline__ void encode16(const float (&x)[3], int h, float (&pe)
     for (int q = 2 * half + 2; q < KS; ++q) pe[q] = 0.f;
 }
 
-// Row f1 (FUSED): the feature gather runs inside this kernel.  A lane (sample j, half hh) works out its own operands of the two bias
-// nets straight from the channel-last sources -- nothing per sample is read but z, nothing is written but raw:
-//   stage-1 volume (hh = 0) / stage-2 volume (hh = 1): all eight channels            -> bd step 0
-//   stage-3 volume: channels 4hh .. 4hh+3 of all eight corners                       -> bd step 1, elements 0..3
-//   source view 2p + hh of pair p: colour + mask -> bd (elements 4..7 of step 1, then two pairs per step), image features -> bc step p
-//   reference projection, confidence: both halves (same values)
-// Arithmetic and accumulation order per feature are gather_cl.hip's (bit-identical features); the weight stream is packed in this
-// operand order (precision 3, build_pack_index_bf16).
-struct FusedGather {
-    int S, V, H, W;
-    int vol_d[3], vol_h[3], vol_w[3];
-    // the channel-last sources, each its own array (ABI v5, ucnerf_cl_sources: read in place or repacked); offsets inside one are 32-bit
-    const char* vol[3];      // [D,h,w,8]
-    const char* feat;        // [V,H,W,8] image features
-    const char* col;         // [V,H,W,col_px / 4] colours
-    unsigned col_px;         // bytes per colour pixel: 12 or 16 (bf16: 8)
-    const float* conf;
-    const float* rays_o;
-    const float* rays_d;
-    const float* z;
-    const float* near_far;
-    float near, far;
-    float w2c_ref[12], K_ref[9];
-    const float* w2cs;
-    const float* Ks;
-    unsigned div_m, div_sh;
-    // COORDS instantiation: coordinates GIVEN by the caller (what rendering() of the reference receives from build_rays / build_rays_test,
-    // network/renderer.py:215-255) instead of derived from (ray, depth): world points, the three stage copies, the encoded copy -- [M,3] each
-    const float* pts_in;
-    const float* ndc_in[3];
-    const float* ndc_enc;
-    int s16;                 // the channel-last arrays hold bf16 (ucnerf_cl_sources.bf16): 16-byte voxels / feature pixels, 8-byte colours
-    // RAYGEN instantiation (ABI v4 gen_rays / gen_depths: ucnerf_ray_gen_sample folded into this launch): pixels and jitter draws in, and the rays,
-    // depths and view-direction features the launch generates are WRITTEN for the launches behind it (compositing, re-sampling, the fine pass)
-    const float* gen_xs;     // [n] pixel columns / rows
-    const float* gen_ys;
-    const float* gen_noise;  // [n,S] or NULL (perturb == 0)
-    float gen_K[4];          // K00, K02, K11, K12 of the target camera
-    float gen_R[12];         // its c2w, row-major 3x4
-    float gen_Q[12];         // rotation of the view-direction feature (w2c_dir)
-    float gen_perturb;
-    int gen_lindisp;
-    float* gen_rays_d;       // [n,3] out
-    float* gen_z;            // [n,S] out
-    float* gen_angle;        // [n,3] out
-    // TAIL instantiation (passes of at most three rounds of tiles): tiles are dealt in whole rays to blocks (tail_rpb rays = tail_rpb * tail_tpr
-    // consecutive tiles per block) and, when its last tile is done, a block composites its rays itself (K7, composite_device.h) and -- coarse
-    // pass -- draws the fine depths from them (K8 + K9, sample_pdf_device.h): one launch for K3 .. K9 of the pass
-    int tail_rpb, tail_tpr, tail_resample;
-    int tail_spb;            // samples per block = tail_rpb * S: the block's tiles start at ITS first sample (round 5: S need not be a multiple of 32,
-                             // e.g. the 90 cascade samples of rendering()), so a block's last tile may be partly filled
-    // view-direction features made in the block's prologue from the rays' directions (round 5: rendering() hands over rays_d and a rotation that
-    // lives on the device -- no ucnerf_dir_feature launch): angle = (d / |d|) @ Q^T written to tail_dir_out [n,3], which the tiles then read
-    const float* tail_dir_Q;     // [>=3,4] DEVICE, or NULL: the features are given (ucnerf_mlp_params.dirs)
-    float* tail_dir_out;
-    ucnerf_composite_params tail_c;
-    ucnerf_sample_pdf_params tail_s;
-};
-[[maybe_unused]] constexpr int FUSED_MAX_V = 8;    // (seven and eight views: with a two-slot weight ring, fused_ring_slots)
 constexpr int VIEW_TAB = 24;      // floats per source view in the LDS table: w2c (12), K (9), pad
 
 template <bool TILED, int NSRC, int TERMS, int SAVE, bool FUSED = false, bool COORDS = false, bool S16 = false, bool RAYGEN = false, bool TAIL = false>       // TAIL (FUSED only): see FusedGather; RAYGEN (FUSED only): rays and stratified depths generated in the tile prologue; TERMS 3: split-bf16 (fp32-grade), 1: plain bf16 (the hi*hi term only); SAVE: training forward keeping the activation sets (1: fp32, 2: the 24-bit format of p24.h); COORDS (FUSED only): sample coordinates given; S16 (FUSED only): bf16 channel-last sources
@@ -1324,276 +1129,9 @@ constexpr size_t bf16_smem_bytes_fused(int v) {
 }
 static_assert(bf16_smem_bytes_fused(6) <= 160 * 1024 && bf16_smem_bytes_fused(8) <= 160 * 1024, "the fused kernel's LDS image must fit the CU");
 
-// `save` (TERMS = 3 only): the training forward -- the activation sets of MlpSaved are written for ucnerf_mlp_bwd (saved_valid = 1)
-#if UCNERF_BF16_BUILD_TAIL
-// the TAIL instantiations (this build's only code objects): `blocks` = ceil(rays / fg->tail_rpb)
-int launch_fused_tail(const ucnerf_mlp_params* p, const BGeom* g, int n_tiles, const FusedGather* fg, int blocks, hipStream_t st) {
-    MlpSaved sv;
-    memset(&sv, 0, sizeof(sv));
-    unsigned* const gword = split_guard().word;          // (checked by launch_bf16, this launcher's only caller)
-    const int v = p->cfg.n_src;
-    const size_t smem_f = bf16_smem_bytes_fused(v);
-    static_assert(BW * (sizeof(PdfShared<128, 512>) + (128 + 2) * sizeof(float)) <= bf16_smem_bytes_fused(1), "the rays' LDS arrays re-use the kernel's image");
-    dim3 grid(blocks), block(64 * BW);
-#define X(N)                                                                                                                   \
-    if (v == N && !fg->pts_in) {                                                                                               \
-        const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>;                 \
-        if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, compositing in the tail)")) return rc; \
-        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg, gword); \
-    }                                                                                                                          \
-    if (v == N && fg->pts_in) {      /* coordinates given: what rendering() hands over (network/renderer.py:215-255) */       \
-        const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>;                  \
-        if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, given coordinates, compositing in the tail)")) return rc; \
-        hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>), grid, block, smem_f, st, *p, *g, n_tiles, sv, *fg, gword); \
-    }
-    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#undef X
-    return check_launch("mlp_fwd (bf16x3, gather fused, compositing in the tail)");
-}
-#else
-int launch_fused_tail(const ucnerf_mlp_params* p, const BGeom* g, int n_tiles, const FusedGather* fg, int blocks, hipStream_t st);      // the TAIL build of this file
-
-static int launch_bf16(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st, const FusedGather* fuse = nullptr) {
-    UCNERF_REQUIRE(p, "mlp_fwd: null params");
-    if (p->m == 0) return UCNERF_OK;
-    UCNERF_REQUIRE(p->dirs && p->wstream && p->raw && (fuse || (p->pts && p->feats)), "mlp_fwd: null pointer");
-    UCNERF_REQUIRE((p->cfg.precision == 3) == (fuse != nullptr), "mlp_fwd: a weight stream packed with precision 3 serves the render pass with the gather "
-                   "fused into the MLP kernel and nothing else (ucnerf_render_fused_fwd)");
-    UCNERF_REQUIRE(!p->encoded && !p->pts_stride && !p->dirs_stride, "mlp_fwd (bf16x3): encoded / strided inputs are only available in f32 precision");
-    UCNERF_REQUIRE(p->dirs_per_sample || p->S > 0, "mlp_fwd: S must be > 0 when dirs are per ray");
-    UCNERF_REQUIRE(((uintptr_t)p->wstream & 15) == 0 && ((uintptr_t)p->raw & 15) == 0, "mlp_fwd: wstream/raw must be 16-byte aligned");
-    Bf16Layout B;
-    UCNERF_REQUIRE(bf16_layout(p->cfg.n_src, &B), "mlp_fwd: n_src %d outside 1..8", p->cfg.n_src);
-    // the guarded split: this build's kernels take the status word (UCNERF_SPLIT_GUARD) or the optional condition word of a replay
-    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0), "mlp_fwd: range detection is compiled into the guarded fp16-term "
-                   "kernels only (ucnerf_*_guarded with cfg.operand 1)");
-    UCNERF_REQUIRE(split_guard().mode == GUARD_NONE || (split_guard().word && !save), "mlp_fwd: a guarded or conditional launch needs its status word "
-                   "and serves the inference forward");
-    unsigned* const gword = split_guard().word;
-    const int n_tiles = cdiv(p->m, 32);
-    const int cus = device_cus();
-    if (cus <= 0) return fail(UCNERF_EHIP, "mlp_fwd: no device");
-    int blocks = cdiv(n_tiles, BW);
-    const int cap = p->max_blocks > 0 ? p->max_blocks : UCNERF_BF16_WPS * 4 / BW * cus;      // blocks per CU = waves per SIMD * 4 / BW
-    // fewer tiles than wave slots: rather every CU with one wave per SIMD than half the CUs with two (tiles are dealt wave-major, see the kernel)
-    if (BW == 8 && UCNERF_BF16_IDLE_SKIP && blocks < cap) { const int spread = cdiv(n_tiles, 4); blocks = spread < cap ? spread : cap; }
-    if (blocks > cap) blocks = cap;
-    BGeom g;
-    g.F = B.F; g.kd16 = B.kd16; g.kc16 = B.kc16; g.f_img = 24 + 4 * B.v; g.slots = B.slots;
-    g.feat_stride = p->feat_stride ? p->feat_stride : B.F;
-    g.const_off_bytes = (int)B.const_off_bytes;
-    // One instantiation per source-view count (1..8: SCARED scripts 6, Hamlyn 3, the reference's opt.py default 4, ...):
-    // with the section lengths known at compile time no instantiation carries the spills of a runtime-length version.
-    // This translation unit is compiled twice (uc_nerf_amd/build.py): -DUCNERF_BF16_BUILD_TERMS=3 (bf16x3) and =1 (bf16).
-    const size_t smem = bf16_smem_bytes();
-    dim3 grid(blocks), block(64 * BW);
-    const bool tiled = p->feats_tiled != 0;
-    constexpr int K = UCNERF_BF16_BUILD_TERMS;
-    MlpSaved sv;
-    memset(&sv, 0, sizeof(sv));
-    FusedGather fg;
-    memset(&fg, 0, sizeof(fg));
-#define UCNERF_BF16_FOR_ALL(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#if UCNERF_BF16_BUILD_TERMS == 3
-    if (fuse) {
-        UCNERF_REQUIRE(!save && B.v <= FUSED_MAX_V, "mlp_fwd (gather fused): inference forward, n_src <= %d", FUSED_MAX_V);
-        fg = *fuse;
-        UCNERF_REQUIRE(!(fg.s16 && fg.pts_in), "mlp_fwd (gather fused): bf16 channel-last sources are served on derived coordinates only (given coordinates: fp32 copies, "
-                       "or the two-kernel pass)");
-        if (fg.tail_rpb > 0) {      // the launch composites its rays itself (small passes, render.hip): whole rays per block, which it also generates when asked to
-            UCNERF_REQUIRE(!fg.s16 && !(fg.gen_xs && (fg.near_far || fg.pts_in)) && p->max_blocks <= 0, "mlp_fwd (gather fused): compositing in the tail goes with fp32 sources (and generated rays with derived coordinates)");
-            return launch_fused_tail(p, &g, n_tiles, &fg, cdiv(fg.tail_c.n, fg.tail_rpb), st);
-        }
-        UCNERF_REQUIRE(!fg.gen_xs || (!fg.s16 && !fg.pts_in && !fg.near_far && B.v <= 6), "mlp_fwd (gather fused): generated rays go with fp32 source copies, derived "
-                       "coordinates, the scene's depth range and at most six source views");
-        const size_t smem_f = bf16_smem_bytes_fused(B.v);
-#define X(N)                                                                                                                   \
-        if (B.v == N && !fg.pts_in && fg.s16) {                                                                                \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>;                           \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, bf16 sources)")) return rc;      \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
-        }                                                                                                                      \
-        if (B.v == N && !fg.pts_in && !fg.s16 && !fg.gen_xs) {                                                                 \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true>;                                        \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused)")) return rc;                    \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
-        }                                                                                                                      \
-        if (B.v == N && fg.pts_in) {                                                                                           \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, true>;                                  \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, given coordinates)")) return rc; \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
-        }
-        UCNERF_BF16_FOR_ALL(X)
-#undef X
-        // rays generated inside the launch (ABI v4 gen_rays / gen_depths): one to six source views (seven and eight spill 24 bytes per lane)
-#define X(N)                                                                                                                   \
-        if (B.v == N && fg.gen_xs) {                                                                                           \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>;                    \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem_f, "mlp_fwd (bf16x3, gather fused, rays generated)")) return rc;    \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>), grid, block, smem_f, st, *p, g, n_tiles, sv, fg, gword); \
-        }
-        X(1) X(2) X(3) X(4) X(5) X(6)
-#undef X
-        return check_launch("mlp_fwd (bf16x3, gather fused)");
-    }
-    if (save) {
-        sv = *save;
-        UCNERF_REQUIRE(sv.p24 || !tiled, "mlp_fwd_train (bf16x3): fp32 activation sets serve the layer-by-layer backward, which reads row-major features");
-#define X(N)                                                                                                                   \
-        if (B.v == N && !tiled && !sv.p24) {                                                                                   \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<false, N, 3, 1>;                                                 \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3)")) return rc;                              \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 1>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);              \
-        }                                                                                                                      \
-        if (B.v == N && !tiled && sv.p24) {                                                                                    \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<false, N, 3, 2>;                                                 \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3, 24-bit sets)")) return rc;                 \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);              \
-        }                                                                                                                      \
-        if (B.v == N && tiled) {                                                                                               \
-            const void* fn = (const void*)mlp_fwd_bf16_kernel<true, N, 3, 2>;                                                  \
-            if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd_train (bf16x3, tiled features, 24-bit sets)")) return rc; \
-            hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, 3, 2>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);               \
-        }
-        UCNERF_BF16_FOR_ALL(X)
-#undef X
-        return check_launch("mlp_fwd_train (bf16x3)");
-    }
-#else
-    UCNERF_REQUIRE(!save, "mlp_fwd_train: plain bf16 has no training forward");
-#endif
-#define X(N)                                                                                                                   \
-    if (B.v == N) {                                                                                                            \
-        const void* fn = tiled ? (const void*)mlp_fwd_bf16_kernel<true, N, K, false> : (const void*)mlp_fwd_bf16_kernel<false, N, K, false>; \
-        if (int rc = ensure_dynamic_lds(fn, (int)smem, "mlp_fwd (bf16)")) return rc;                                          \
-        if (tiled) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);    \
-        else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, N, K, false>), grid, block, smem, st, *p, g, n_tiles, sv, fg, gword);         \
-    }
-    UCNERF_BF16_FOR_ALL(X)
-#undef X
-#undef UCNERF_BF16_FOR_ALL
-    return check_launch("mlp_fwd_bf16");
-}
-
-// (the timing-experiment switches of rounds 1-3 -- UCNERF_BF16_EXP, NO_PK, SPLIT_DOT, FUSED_FOOT_UNDER_GEMM, the DIAG stamps -- were taken out of
-//  this file in round 4, their numbers are in profiles/r0N_experiments.md and DESIGN.md; what is left are structural parameters)
-#define UCNERF_BF16_FLAGS UCNERF_FLAG(UCNERF_BF16_BW) UCNERF_FLAG(UCNERF_BF16_NBUF) UCNERF_FLAG(UCNERF_BF16_WPS) UCNERF_FLAG(UCNERF_BF16_HINT_V) \
-    UCNERF_FLAG(UCNERF_BF16_PRIO_VALU) UCNERF_FLAG(UCNERF_BF16_PRIO_GEMM) UCNERF_FLAG(UCNERF_BF16_IDLE_SKIP) UCNERF_FLAG(UCNERF_BF16_WAVE_MAJOR)
-#if UCNERF_BF16_BUILD_TERMS == 3
-const char* build_flags_mlp_bf16x3() { return "mlp_bf16x3: " UCNERF_BF16_FLAGS; }
-#else
-const char* build_flags_mlp_bf16_plain() { return "mlp_bf16_plain: " UCNERF_BF16_FLAGS; }
-#endif
-
-#if UCNERF_BF16_BUILD_TERMS == 3
-#if !UCNERF_OPERAND_FP16
-int launch_mlp_fwd_bf16x3_h16(const ucnerf_mlp_params* p, hipStream_t st);                   // the fp16-term builds of this file (cfg.operand == 1)
-int launch_mlp_fwd_bf16x3_gather_h16(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st, const ucnerf_composite_params* tail_c,
-                                     const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out);
-int launch_pack_bf16_h16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st);
-int launch_pack_bf16_tab_h16(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st);
-int launch_mlp_fwd_bf16x3_g16(const ucnerf_mlp_params* p, hipStream_t st);                   // ... and their twins with range detection (UCNERF_SPLIT_GUARD)
-int launch_mlp_fwd_bf16x3_gather_g16(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st, const ucnerf_composite_params* tail_c,
-                                     const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out);
-int launch_pack_bf16_g16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st);
-int launch_pack_bf16_tab_g16(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st);
-#endif
-int launch_mlp_fwd_bf16x3(const ucnerf_mlp_params* p, hipStream_t st) {
-    UCNERF_REQUIRE(p, "mlp_fwd: null params");
-    UCNERF_REQUIRE(p->cfg.operand == 0 || p->cfg.operand == 1, "mlp_fwd: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", p->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16x3, p, st);
-    return launch_bf16(p, nullptr, st);
-}
-int launch_mlp_fwd_bf16x3_save(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st) {
-    UCNERF_REQUIRE(p && p->cfg.operand == 0, "mlp_fwd_train: the training forward keeps its activations for a backward that splits them into bf16 terms "
-                   "(cfg.operand 0); fp16 terms serve the inference forward");
-    return launch_bf16(p, save, st);
-}
-
-// called by render.hip: gather + PE + MLP of one pass in ONE launch (row f1), from the channel-last sources and (ray, depth)
-// `tail_c` (optional): the launch also composites the pass's rays (and, with `tail_s`, re-samples from them) -- see FusedGather
-int check_cl_sources(const ucnerf_render_params* p, const char* who);      // gather_cl.hip
-int launch_mlp_fwd_bf16x3_gather(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st,
-                                 const ucnerf_composite_params* tail_c, const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out) {
-    UCNERF_REQUIRE(rp->cfg.operand == 0 || rp->cfg.operand == 1, "render (gather fused): cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", rp->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(rp->cfg.operand, launch_mlp_fwd_bf16x3_gather, rp, dirs, raw, st, tail_c, tail_s, tail_dir_out);
-    const long long M = (long long)rp->n * rp->S;
-    UCNERF_REQUIRE(M < (1ll << 31), "render (gather fused): %lld samples in one pass (limit 2^31 - 1)", M);
-    if (int rc = check_cl_sources(rp, "render (gather fused)")) return rc;
-    ucnerf_mlp_params m;
-    memset(&m, 0, sizeof(m));
-    m.cfg = rp->cfg; m.m = (int)M; m.S = rp->S; m.max_blocks = rp->max_blocks; m.dirs = dirs; m.wstream = rp->wstream; m.raw = raw;
-    FusedGather f;
-    memset(&f, 0, sizeof(f));
-    f.S = rp->S; f.V = rp->cfg.n_src; f.H = rp->H; f.W = rp->W;
-    for (int k = 0; k < 3; ++k) {
-        f.vol_d[k] = rp->vol_d[k]; f.vol_h[k] = rp->vol_h[k]; f.vol_w[k] = rp->vol_w[k];
-        f.vol[k] = reinterpret_cast<const char*>(rp->cl.vol[k]);
-    }
-    f.s16 = rp->cl.bf16 ? 1 : 0;
-    f.feat = reinterpret_cast<const char*>(rp->cl.img_feat); f.col = reinterpret_cast<const char*>(rp->cl.imgs);
-    f.col_px = rp->cl.bf16 ? 8u : 4u * (unsigned)rp->cl.rgb_stride;
-    f.conf = rp->conf; f.rays_o = rp->rays_o; f.rays_d = rp->rays_d; f.z = rp->z; f.near_far = rp->near_far;
-    f.near = rp->near; f.far = rp->far;
-    memcpy(f.w2c_ref, rp->w2c_ref, sizeof(f.w2c_ref));
-    memcpy(f.K_ref, rp->K_ref, sizeof(f.K_ref));
-    f.w2cs = rp->w2cs; f.Ks = rp->intrinsics;
-    f.pts_in = rp->pts_in; f.ndc_in[0] = rp->ndc1_in; f.ndc_in[1] = rp->ndc2_in; f.ndc_in[2] = rp->ndc3_in; f.ndc_enc = rp->ndc_in;
-    if (rp->gen_rays) {          // ABI v4: the launch generates rays and stratified depths itself (validated by ucnerf_render_fused_fwd)
-        const ucnerf_ray_gen_params* gr = rp->gen_rays;
-        const ucnerf_sample_stratified_params* gs = rp->gen_depths;
-        f.gen_xs = gr->xs; f.gen_ys = gr->ys; f.gen_noise = gs->perturb > 0.f ? gs->noise : nullptr;
-        f.gen_K[0] = gr->K[0]; f.gen_K[1] = gr->K[2]; f.gen_K[2] = gr->K[4]; f.gen_K[3] = gr->K[5];
-        memcpy(f.gen_R, gr->c2w, sizeof(f.gen_R));
-        memcpy(f.gen_Q, gr->w2c_dir, sizeof(f.gen_Q));
-        f.gen_perturb = gs->perturb; f.gen_lindisp = gs->lindisp;
-        f.gen_rays_d = gr->rays_d; f.gen_z = gs->z; f.gen_angle = gr->angle;      // (`dirs` is not read: every lane derives its ray's feature itself)
-    }
-    {   // magic for idx / S (gather_cl.hip)
-        unsigned l = 1;
-        while ((1u << l) < (unsigned)rp->S) ++l;
-        f.div_m = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)rp->S - 1) / (unsigned)rp->S);
-        f.div_sh = l - 1;
-    }
-    if (tail_c) {
-        const int cus = device_cus();
-        if (cus <= 0) return fail(UCNERF_EHIP, "mlp_fwd: no device");
-        f.tail_rpb = cdiv(rp->n, cus); f.tail_tpr = cdiv(rp->S, 32); f.tail_resample = tail_s ? 1 : 0;
-        f.tail_spb = f.tail_rpb * rp->S;
-        if (tail_dir_out) { f.tail_dir_Q = rp->w2c_dir_dev; f.tail_dir_out = tail_dir_out; }      // (render.hip: the features are made in the blocks' prologues)
-        f.tail_c = *tail_c;
-        if (tail_s) f.tail_s = *tail_s;
-    }
-    return launch_bf16(&m, nullptr, st, &f);
-}
-#else
-#if !UCNERF_OPERAND_FP16
-int launch_mlp_fwd_bf16_plain_h16(const ucnerf_mlp_params* p, hipStream_t st);
-int launch_mlp_fwd_bf16_plain_g16(const ucnerf_mlp_params* p, hipStream_t st);
-#endif
-int launch_mlp_fwd_bf16_plain(const ucnerf_mlp_params* p, hipStream_t st) {
-    UCNERF_REQUIRE(p, "mlp_fwd: null params");
-    UCNERF_REQUIRE(p->cfg.operand == 0 || p->cfg.operand == 1, "mlp_fwd: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", p->cfg.operand);
-    UCNERF_OPERAND_DISPATCH(p->cfg.operand, launch_mlp_fwd_bf16_plain, p, st);
-    return launch_bf16(p, nullptr, st);
-}
-#endif
-
-#if UCNERF_BF16_BUILD_TERMS == 3
-int64_t bf16_index_count(const ucnerf_mlp_config* cfg) {
-    Bf16Layout B;
-    if (!bf16_layout(cfg->n_src, &B)) return -1;
-    return (int64_t)B.slots * (SLOT_BYTES / 2) + CONST_FLOATS;
-}
-
-int64_t bf16_stream_floats(const ucnerf_mlp_config* cfg) {
-    Bf16Layout B;
-    if (!bf16_layout(cfg->n_src, &B)) return -1;
-    return B.total_bytes / 4;
-}
-
-// ONE launch for the whole stream from the flat parameter vector (round 5: the evaluation loop re-packs in every rendering() call -- two launches were
-// 5 us of GPU time and two launches' host time per 1024-pixel chunk): blocks [0, nb16) convert the bf16 half-steps, the rest copy the fp32 constants
+#if UCNERF_BF16_BUILD_TERMS == 3 && !UCNERF_BF16_BUILD_TAIL
+// ------------------------------------------------------------------------------------------------ packing the weight stream (launch_pack, mlp_bf16_host.hip)
+// blocks [0, nb16) convert the 16-bit half-steps, the rest copy the fp32 constants
 // gword: as in mlp_fwd_bf16_kernel -- `run_if` (NULL in an unconditional pack), or the status word of the guarded fp16 packers, which OR bit 1 into it
 // for a weight whose hi term is not finite or reaches 65 504 (the unguarded fp16 packers turn such a weight into hi = inf, lo = -inf)
 #if UCNERF_SPLIT_GUARD
@@ -1629,21 +1167,7 @@ __global__ void pack_all_flat_kernel(const float* __restrict__ flat, const int32
     }
 }
 
-int launch_pack_bf16(const ucnerf_mlp_config* cfg, const float* flat, const int32_t* idx, float* out, hipStream_t st) {
-    UCNERF_REQUIRE(cfg->operand == 0 || cfg->operand == 1, "mlp_pack: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", cfg->operand);
-    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16, cfg, flat, idx, out, st);
-    Bf16Layout B;
-    UCNERF_REQUIRE(bf16_layout(cfg->n_src, &B), "mlp_pack: n_src %d outside 1..8", cfg->n_src);
-    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0) && (split_guard().mode == GUARD_NONE || split_guard().word),
-                   "mlp_pack: range detection is compiled into the guarded fp16 packers only (ucnerf_mlp_pack*_guarded with cfg.operand 1), with a status word");
-    const int64_t n16 = (int64_t)B.slots * (SLOT_BYTES / 2);
-    const int nb16 = cdiv(n16, 256), nbc = cdiv(CONST_FLOATS, 256);
-    hipLaunchKernelGGL(pack_all_flat_kernel, dim3(nb16 + nbc), dim3(256), 0, st, flat, idx, reinterpret_cast<unsigned short*>(out), n16,
-                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16, split_guard().word);
-    return check_launch("mlp_pack (bf16x3)");
-}
-
-// ONE launch for the whole stream (the drop-in re-packs in every no_grad call): blocks [0, nb16) convert the bf16 half-steps, the rest copy the fp32 constants
+// the same from the tensors of a torch module (ParamTable, common.h)
 __global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ idx, unsigned short* __restrict__ out16, int64_t n16, float* __restrict__ outc, int nc, int nb16,
                                     unsigned* gword) {
 #if !UCNERF_SPLIT_GUARD
@@ -1671,22 +1195,60 @@ __global__ void pack_all_tab_kernel(ParamTable t, const int32_t* __restrict__ id
         if (i < nc) { const int32_t k = idx[n16 + i]; outc[i] = k >= 0 ? param_table_load(&l, k) : 0.f; }
     }
 }
+#endif
 
-int launch_pack_bf16_tab(const ucnerf_mlp_config* cfg, const ParamTable& t, const int32_t* idx, float* out, hipStream_t st) {
-    UCNERF_REQUIRE(cfg->operand == 0 || cfg->operand == 1, "mlp_pack_tensors: cfg.operand %d (0 = bf16 terms, 1 = fp16 terms)", cfg->operand);
-    UCNERF_OPERAND_DISPATCH(cfg->operand, launch_pack_bf16_tab, cfg, t, idx, out, st);
-    Bf16Layout B;
-    UCNERF_REQUIRE(bf16_layout(cfg->n_src, &B), "mlp_pack: n_src %d outside 1..8", cfg->n_src);
-    UCNERF_REQUIRE((split_guard().mode == GUARD_DETECT) == (UCNERF_SPLIT_GUARD != 0) && (split_guard().mode == GUARD_NONE || split_guard().word),
-                   "mlp_pack: range detection is compiled into the guarded fp16 packers only (ucnerf_mlp_pack*_guarded with cfg.operand 1), with a status word");
-    const int64_t n16 = (int64_t)B.slots * (SLOT_BYTES / 2);
-    const int nb16 = cdiv(n16, 256), nbc = cdiv(CONST_FLOATS, 256);
-    hipLaunchKernelGGL(pack_all_tab_kernel, dim3(nb16 + nbc), dim3(256), 0, st, t, idx, reinterpret_cast<unsigned short*>(out), n16,
-                       reinterpret_cast<float*>(reinterpret_cast<char*>(out) + B.const_off_bytes), CONST_FLOATS, nb16, split_guard().word);
-    return check_launch("mlp_pack_tensors (bf16x3)");
+// ------------------------------------------------------------------------------------------------ what this build exports
+// The instantiations of this build, under the launch conditions that select them (MlpVariant, mlp_bf16.h): naming one here is what compiles it.
+template <int N>
+static void add_kernels(Bf16Build& b) {
+    auto set = [&](MlpVariant var, MlpFwdKernel* kernel) { b.fwd[var][N - 1] = kernel; };
+#if UCNERF_BF16_BUILD_TAIL
+    set(MV_TAIL, mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, false, true>);
+    set(MV_TAIL_COORDS, mlp_fwd_bf16_kernel<true, N, 3, false, true, true, false, false, true>);
+#else
+    set(MV_ROWS, mlp_fwd_bf16_kernel<false, N, UCNERF_BF16_BUILD_TERMS, false>);
+    set(MV_TILED, mlp_fwd_bf16_kernel<true, N, UCNERF_BF16_BUILD_TERMS, false>);
+#if UCNERF_BF16_BUILD_TERMS == 3
+    set(MV_SAVE_F32, mlp_fwd_bf16_kernel<false, N, 3, 1>);
+    set(MV_SAVE_P24, mlp_fwd_bf16_kernel<false, N, 3, 2>);
+    set(MV_SAVE_P24_TILED, mlp_fwd_bf16_kernel<true, N, 3, 2>);
+    set(MV_FUSED, mlp_fwd_bf16_kernel<true, N, 3, false, true>);
+    set(MV_FUSED_COORDS, mlp_fwd_bf16_kernel<true, N, 3, false, true, true>);
+    set(MV_FUSED_S16, mlp_fwd_bf16_kernel<true, N, 3, false, true, false, true>);
+    if constexpr (N <= 6) set(MV_FUSED_RAYGEN, mlp_fwd_bf16_kernel<true, N, 3, false, true, false, false, true>);      // (seven and eight spill 24 bytes per lane)
+#endif
+#endif
+    if constexpr (N < 8) add_kernels<N + 1>(b);
 }
 
-#endif   // UCNERF_BF16_BUILD_TERMS == 3
-#endif   // !UCNERF_BF16_BUILD_TAIL
+// (the timing-experiment switches of rounds 1-3 -- UCNERF_BF16_EXP, NO_PK, SPLIT_DOT, FUSED_FOOT_UNDER_GEMM, the DIAG stamps -- were taken out of
+//  this file in round 4, their numbers are in profiles/r0N_experiments.md and DESIGN.md; what is left are structural parameters)
+#define UCNERF_BF16_FLAGS UCNERF_FLAG(UCNERF_BF16_BW) UCNERF_FLAG(UCNERF_BF16_NBUF) UCNERF_FLAG(UCNERF_BF16_WPS) UCNERF_FLAG(UCNERF_BF16_HINT_V) \
+    UCNERF_FLAG(UCNERF_BF16_PRIO_VALU) UCNERF_FLAG(UCNERF_BF16_PRIO_GEMM) UCNERF_FLAG(UCNERF_BF16_IDLE_SKIP) UCNERF_FLAG(UCNERF_BF16_WAVE_MAJOR)
+
+const Bf16Build* bf16_build() {
+    static const Bf16Build build = [] {
+        Bf16Build b{};
+        add_kernels<1>(b);
+#if UCNERF_BF16_BUILD_TAIL
+        static_assert(BW * (sizeof(PdfShared<128, 512>) + (128 + 2) * sizeof(float)) <= bf16_smem_bytes_fused(1), "the rays' LDS arrays re-use the kernel's image");
+        b.build_flags = "mlp_bf16_tail: " UCNERF_BF16_FLAGS;
+#elif UCNERF_BF16_BUILD_TERMS == 3
+        b.pack_flat = pack_all_flat_kernel;
+        b.pack_tab = pack_all_tab_kernel;
+        b.build_flags = "mlp_bf16x3: " UCNERF_BF16_FLAGS;
+#else
+        b.build_flags = "mlp_bf16_plain: " UCNERF_BF16_FLAGS;
+#endif
+        b.guard = UCNERF_SPLIT_GUARD != 0;
+        b.waves = BW;
+        b.blocks_per_cu = UCNERF_BF16_WPS * 4 / BW;
+        b.spread = BW == 8 && UCNERF_BF16_IDLE_SKIP;
+        b.lds = bf16_smem_bytes();
+        for (int v = 1; v <= 8; ++v) b.lds_fused[v - 1] = bf16_smem_bytes_fused(v);
+        return b;
+    }();
+    return &build;
+}
 
 }  // namespace ucnerf

@@ -11,13 +11,13 @@
 // flat parameter-gradient vector (same layout as the flat parameter vector), so no unpacking is needed.
 #include "common.h"
 #include "mlp_layout.h"
+#include "mlp_bf16.h"
 #include "mlp_bwd_parts.h"
 #include "mfma_split.h"
 
 namespace ucnerf {
 
 int launch_mlp_fwd(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st);
-int launch_mlp_fwd_bf16x3_save(const ucnerf_mlp_params* p, const MlpSaved* save, hipStream_t st);      // mlp_bf16.hip
 int launch_embed_strided(int m, int n_freqs, int layout, const float* x, float* out, int out_stride, hipStream_t st);      // rays.hip
 
 // 4 consecutive parameters (parameter tensors are only 4-byte aligned inside the flat vector)

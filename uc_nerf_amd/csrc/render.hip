@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <mutex>
 #include "mlp_layout.h"
+#include "mlp_bf16.h"
 
 namespace ucnerf {
 
@@ -59,8 +60,6 @@ __global__ void __launch_bounds__(256) render_points_kernel(PointsArgs a) {
 
 int launch_gather_cl(const ucnerf_render_params* p, float* feats, int tiled, float* ndc, hipStream_t st);
 int check_cl_sources(const ucnerf_render_params* p, const char* who);                                              // gather_cl.hip
-int launch_mlp_fwd_bf16x3_gather(const ucnerf_render_params* rp, const float* dirs, float* raw, hipStream_t st,
-                                 const ucnerf_composite_params* tail_c, const ucnerf_sample_pdf_params* tail_s, float* tail_dir_out);   // mlp_bf16.hip
 
 struct Workspace {
     float *pts, *ndc1, *ndc2, *ndc3, *ndc, *angle, *feats, *raw;
