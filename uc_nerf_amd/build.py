@@ -25,8 +25,8 @@ VARIANTS = [("mlp_bf16.hip", "mlp_bf16_plain.o", ["-DUCNERF_BF16_BUILD_TERMS=1"]
             ("mlp_bf16.hip", "mlp_g16.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1"]),
             ("mlp_bf16.hip", "mlp_g16_plain.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1", "-DUCNERF_BF16_BUILD_TERMS=1"]),
             ("mlp_bf16.hip", "mlp_g16_tail.o", ["-DUCNERF_OPERAND_FP16=1", "-DUCNERF_SPLIT_GUARD=1", "-DUCNERF_BF16_BUILD_TAIL=1"])]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "mlp_layout.h"), os.path.join(CSRC, "sincos_cw.h"), os.path.join(CSRC, "gather_cl_device.h"), os.path.join(CSRC, "mlp_bwd_parts.h"), os.path.join(CSRC, "p24.h"), os.path.join(CSRC, "composite_device.h"), os.path.join(CSRC, "sample_pdf_device.h"), os.path.join(CSRC, "raygen_device.h"), os.path.join(CSRC, "mfma_split.h"), os.path.join(CSRC, "mlp_bf16.h"),
-           os.path.join(HERE, "..", "include", "ucnerf_hip.h")]
+# every header of csrc/ and the public one: derived, so that a new header is part of the staleness checks and of source_hash() from the start
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(HERE, "..", "include", "ucnerf_hip.h")]
 # -ffp-contract=off: the sample_pdf / sampling kernels reproduce torch-CPU roundings (separate mul and add)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]

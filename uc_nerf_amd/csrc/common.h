@@ -35,6 +35,27 @@ inline int check_launch(const char* what) {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Exact x / d for x < 2^31 by multiply-high: l = ceil(log2 d) (at least 1), m = ceil(2^(31+l) / d) < 2^32, x / d = mulhi(x, m) >> (l - 1).
+// d == 1 has no such m (it would be 2^32): m = 0 stands for it.  The host fills an ExactDiv into a kernel's arguments; the kernel calls quot()
+// and keeps its own test for a divisor of 1 (it tests the divisor, which it holds anyway: testing m instead changes the tuned kernels' code).
+struct ExactDiv {
+    unsigned m, sh;
+    ExactDiv() = default;
+    constexpr explicit ExactDiv(unsigned d) : m(0), sh(0) {
+        unsigned l = 1;
+        while ((1u << l) < d) ++l;
+        m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
+        sh = l - 1;
+    }
+    constexpr __host__ __device__ unsigned quot(unsigned x) const { return (unsigned)(((unsigned long long)x * m) >> 32) >> sh; }   // x / d, d >= 2
+    constexpr unsigned div(unsigned x) const { return m == 0 ? x : quot(x); }            // x / d, any d: the model the static_assert checks
+};
+constexpr bool exact_div_ok(unsigned d) {
+    const ExactDiv q(d);
+    return q.div(0) == 0 && q.div(d - 1) == 0 && q.div(d) == 1 && q.div(0x7fffffffu) == 0x7fffffffu / d;
+}
+static_assert(exact_div_ok(1) && exact_div_ok(2) && exact_div_ok(3) && exact_div_ok(30) && exact_div_ok(90) && exact_div_ok(192) && exact_div_ok(1024), "ExactDiv");
+
 struct Mat34 { float m[12]; };
 struct Mat33 { float m[9]; };
 

@@ -5,34 +5,11 @@
 // 3 = confidence (bilinear, align_corners=False, sampled with the stage-3 grid), 4.. = one per source view
 // (world point -> view pixel; bilinear rgb + in-mask + 8 image-feature channels, align_corners=True).
 // blockIdx.y selects the unit, so every wave runs one code path and consecutive lanes are consecutive
-// samples of a ray (neighbouring voxels -> L2 locality).  grid_sample semantics restated:
-//   align_corners=False: i = ((g+1)*size - 1)/2;  align_corners=True: i = (g+1)/2*(size-1);
-//   border padding: clamp i to [0, size-1] before floor/frac; a corner index == size gets weight 0.
+// samples of a ray (neighbouring voxels -> L2 locality).  grid_sample semantics: geometry_device.h.
 #include "common.h"
+#include "geometry_device.h"
 
 namespace ucnerf {
-
-__device__ __forceinline__ float unnorm(float g, int size, bool align) {
-    float i = align ? (g + 1.f) / 2.f * (float)(size - 1) : ((g + 1.f) * (float)size - 1.f) / 2.f;
-    return fminf(fmaxf(i, 0.f), (float)(size - 1));
-}
-
-struct Lerp {        // one axis of a (bi|tri)linear footprint
-    int i0, i1;      // corner indices (i1 clamped into range; its weight is 0 when it was out of range)
-    float w0, w1;
-};
-
-__device__ __forceinline__ Lerp axis(float g, int size, bool align) {
-    const float x = unnorm(g, size, align);
-    const float f = floorf(x);
-    Lerp a;
-    a.i0 = (int)f;
-    a.w1 = x - f;
-    a.w0 = 1.f - a.w1;
-    a.i1 = a.i0 + 1;
-    if (a.i1 > size - 1) { a.i1 = size - 1; a.w1 = 0.f; }
-    return a;
-}
 
 // feature f of sample s in the output tensor
 __device__ __forceinline__ size_t out_index(const ucnerf_feat_gather_params& p, int F, int s, int f) {
@@ -44,6 +21,7 @@ __device__ __forceinline__ void project_view(const ucnerf_feat_gather_params& p,
     const float* M = p.w2cs + 12 * v;
     const float* K = p.intrinsics + 9 * v;
     const float x = p.pts[3 * (size_t)s], y = p.pts[3 * (size_t)s + 1], z = p.pts[3 * (size_t)s + 2];
+    // written out: with geometry_device.h's project() or project_cl() here feat_gather_fwd_kernel's code changes
     const float cx = x * M[0] + y * M[1] + z * M[2] + M[3];
     const float cy = x * M[4] + y * M[5] + z * M[6] + M[7];
     float cz = x * M[8] + y * M[9] + z * M[10] + M[11];
@@ -51,8 +29,8 @@ __device__ __forceinline__ void project_view(const ucnerf_feat_gather_params& p,
     const float qx = cx * K[0] + cy * K[1] + cz * K[2];
     const float qy = cx * K[3] + cy * K[4] + cz * K[5];
     const float qz = cx * K[6] + cy * K[7] + cz * K[8];
-    *gx = (qx / qz + 0.0f) / (float)(p.W - 1) * 2.0f - 1.0f;
-    *gy = (qy / qz + 0.0f) / (float)(p.H - 1) * 2.0f - 1.0f;
+    *gx = to_grid((qx / qz + 0.0f) / (float)(p.W - 1));
+    *gy = to_grid((qy / qz + 0.0f) / (float)(p.H - 1));
 }
 
 __global__ void __launch_bounds__(256) feat_gather_fwd_kernel(ucnerf_feat_gather_params p) {
@@ -64,8 +42,8 @@ __global__ void __launch_bounds__(256) feat_gather_fwd_kernel(ucnerf_feat_gather
     if (unit < 3) {
         const float* g = (unit == 0 ? p.ndc1 : unit == 1 ? p.ndc2 : p.ndc3) + 3 * (size_t)s;
         const int D = p.vol_d[unit], h = p.vol_h[unit], w = p.vol_w[unit];
-        const Lerp ax = axis(g[0] * 2.f - 1.0f, w, false), ay = axis(g[1] * 2.f - 1.0f, h, false),
-                   az = axis(g[2] * 2.f - 1.0f, D, false);
+        const Lerp ax = axis(to_grid(g[0]), w, false), ay = axis(to_grid(g[1]), h, false),
+                   az = axis(to_grid(g[2]), D, false);
         const float* vol = p.vol[unit];
         const size_t cs = (size_t)D * h * w;
         const size_t o00 = ((size_t)az.i0 * h + ay.i0) * w, o01 = ((size_t)az.i0 * h + ay.i1) * w,
@@ -86,7 +64,7 @@ __global__ void __launch_bounds__(256) feat_gather_fwd_kernel(ucnerf_feat_gather
         }
     } else if (unit == 3) {
         const float* g = p.ndc3 + 3 * (size_t)s;
-        const Lerp ax = axis(g[0] * 2.f - 1.0f, p.W, false), ay = axis(g[1] * 2.f - 1.0f, p.H, false);
+        const Lerp ax = axis(to_grid(g[0]), p.W, false), ay = axis(to_grid(g[1]), p.H, false);
         const float* c = p.conf;
         float acc = c[(size_t)ay.i0 * p.W + ax.i0] * (ay.w0 * ax.w0);
         acc += c[(size_t)ay.i0 * p.W + ax.i1] * (ay.w0 * ax.w1);
@@ -136,8 +114,8 @@ __global__ void __launch_bounds__(256) feat_gather_bwd_kernel(ucnerf_feat_gather
         if (!gv) return;
         const float* g = (unit == 0 ? p.ndc1 : unit == 1 ? p.ndc2 : p.ndc3) + 3 * (size_t)s;
         const int D = p.vol_d[unit], h = p.vol_h[unit], w = p.vol_w[unit];
-        const Lerp ax = axis(g[0] * 2.f - 1.0f, w, false), ay = axis(g[1] * 2.f - 1.0f, h, false),
-                   az = axis(g[2] * 2.f - 1.0f, D, false);
+        const Lerp ax = axis(to_grid(g[0]), w, false), ay = axis(to_grid(g[1]), h, false),
+                   az = axis(to_grid(g[2]), D, false);
         const size_t cs = (size_t)D * h * w;
         const size_t o00 = ((size_t)az.i0 * h + ay.i0) * w, o01 = ((size_t)az.i0 * h + ay.i1) * w,
                      o10 = ((size_t)az.i1 * h + ay.i0) * w, o11 = ((size_t)az.i1 * h + ay.i1) * w;
@@ -164,7 +142,7 @@ __global__ void __launch_bounds__(256) feat_gather_bwd_kernel(ucnerf_feat_gather
     } else if (unit == 3) {
         if (!bp.g_conf) return;
         const float* g = p.ndc3 + 3 * (size_t)s;
-        const Lerp ax = axis(g[0] * 2.f - 1.0f, p.W, false), ay = axis(g[1] * 2.f - 1.0f, p.H, false);
+        const Lerp ax = axis(to_grid(g[0]), p.W, false), ay = axis(to_grid(g[1]), p.H, false);
         const float gc = gf[F - 1];
         atomicAdd(bp.g_conf + (size_t)ay.i0 * p.W + ax.i0, gc * (ay.w0 * ax.w0));
         atomicAdd(bp.g_conf + (size_t)ay.i0 * p.W + ax.i1, gc * (ay.w0 * ax.w1));
@@ -219,7 +197,7 @@ __global__ void __launch_bounds__(256) conf_bwd_kernel(ucnerf_feat_gather_bwd_pa
     const int s = live ? s_raw : p.m - 1;
     const int F = 24 + 12 * p.V + 1, pos = threadIdx.x & 63;
     const float* g = p.ndc3 + 3 * (size_t)s;
-    const Lerp ax = axis(g[0] * 2.f - 1.0f, p.W, false), ay = axis(g[1] * 2.f - 1.0f, p.H, false);
+    const Lerp ax = axis(to_grid(g[0]), p.W, false), ay = axis(to_grid(g[1]), p.H, false);
     const float gc = live ? bp.g_feats[(size_t)s * F + F - 1] : 0.f;
     const int dead = live ? 0 : -1;
     run_atomic_add<1>(bp.g_conf, dead | (ay.i0 * p.W + ax.i0), gc * (ay.w0 * ax.w0), pos);
@@ -242,8 +220,8 @@ __device__ __forceinline__ VolCorners vol_corners(const ucnerf_feat_gather_bwd_p
     const int dead = live ? 0 : -1;                                     // keys of lanes past the end
     const float* g = (unit == 0 ? p.ndc1 : unit == 1 ? p.ndc2 : p.ndc3) + 3 * s;
     const int D = p.vol_d[unit], h = p.vol_h[unit], w = p.vol_w[unit];
-    const Lerp ax = axis(g[0] * 2.f - 1.0f, w, false), ay = axis(g[1] * 2.f - 1.0f, h, false),
-               az = axis(g[2] * 2.f - 1.0f, D, false);
+    const Lerp ax = axis(to_grid(g[0]), w, false), ay = axis(to_grid(g[1]), h, false),
+               az = axis(to_grid(g[2]), D, false);
     const int o00 = (az.i0 * h + ay.i0) * w, o01 = (az.i0 * h + ay.i1) * w,
               o10 = (az.i1 * h + ay.i0) * w, o11 = (az.i1 * h + ay.i1) * w;
     const float w00 = az.w0 * ay.w0, w01 = az.w0 * ay.w1, w10 = az.w1 * ay.w0, w11 = az.w1 * ay.w1;

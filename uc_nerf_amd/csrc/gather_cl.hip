@@ -83,14 +83,15 @@ struct GatherClArgs {
     // GIVEN coordinates (rendering() hands over rays_pts / rays_ndc, network/renderer.py:215-255) instead of (ray, depth)
     const float* pts_in;       // [M,3] world points
     const float* ndc_in[3];    // [M,3] stage coordinates
-    unsigned M, div_m, div_sh; // n * S; idx / S = umulhi(idx, div_m) >> div_sh for idx < 2^31 (S >= 2)
+    unsigned M;                // n * S
+    ExactDiv by_S;             // idx / S for S >= 2
 };
 
 struct SampleIn { unsigned r; float z, dx, dy, dz; };        // what a sample reads before it can compute anything
 
 __device__ __forceinline__ SampleIn sample_in(const GatherClArgs& a, unsigned idx) {
     SampleIn s;
-    s.r = a.S == 1 ? idx : (__umulhi(idx, a.div_m) >> a.div_sh);                     // idx / S (host-side magic, idx < 2^31)
+    s.r = a.S == 1 ? idx : a.by_S.quot(idx);                     // idx / S (idx < 2^31)
     s.z = a.z[idx];
     s.dx = a.rays_d[3 * s.r]; s.dy = a.rays_d[3 * s.r + 1]; s.dz = a.rays_d[3 * s.r + 2];
     return s;
@@ -126,7 +127,7 @@ __device__ __forceinline__ void gather_cl_unit(const GatherClArgs& a, unsigned i
             if (!GIVEN && a.ndc) {
                 a.ndc[3 * (size_t)idx] = u; a.ndc[3 * (size_t)idx + 1] = v; a.ndc[3 * (size_t)idx + 2] = (qz - a.near) / (a.far - a.near);
             }
-            const LerpCl ax = axis_cl(u * 2.f - 1.0f, a.W, false), ay = axis_cl(v * 2.f - 1.0f, a.H, false);
+            const Lerp ax = axis(to_grid(u), a.W, false), ay = axis(to_grid(v), a.H, false);
             const float* c = a.conf;
             float acc = c[(size_t)ay.i0 * a.W + ax.i0] * (ay.w0 * ax.w0);
             acc += c[(size_t)ay.i0 * a.W + ax.i1] * (ay.w0 * ax.w1);
@@ -143,8 +144,8 @@ __device__ __forceinline__ void gather_cl_unit(const GatherClArgs& a, unsigned i
             zn = (qz - nk) / (fk - nk);
         }
         const int D = a.vol_d[unit], hh = a.vol_h[unit], ww = a.vol_w[unit];
-        const LerpCl ax = axis_cl(u * 2.f - 1.0f, ww, false), ay = axis_cl(v * 2.f - 1.0f, hh, false),
-                     az = axis_cl(zn * 2.f - 1.0f, D, false);
+        const Lerp ax = axis(to_grid(u), ww, false), ay = axis(to_grid(v), hh, false),
+                     az = axis(to_grid(zn), D, false);
         const char* vol = (const char*)a.vol[unit];
         // byte offsets of the four (z, y) rows at x0, and the step to x1 (0 at the clamped border)
         const unsigned o00 = (unsigned)((az.i0 * hh + ay.i0) * ww + ax.i0) * VOX, o01 = (unsigned)((az.i0 * hh + ay.i1) * ww + ax.i0) * VOX,
@@ -167,8 +168,8 @@ __device__ __forceinline__ void gather_cl_unit(const GatherClArgs& a, unsigned i
         const int vi = unit - 4;
         float qx, qy, qz;
         project_cl(a.w2cs + 12 * vi, a.Ks + 9 * vi, x, y, w, &qx, &qy, &qz);
-        const float gx = (qx / qz + 0.0f) / (float)(a.W - 1) * 2.0f - 1.0f, gy = (qy / qz + 0.0f) / (float)(a.H - 1) * 2.0f - 1.0f;
-        const LerpCl ax = axis_cl(gx, a.W, true), ay = axis_cl(gy, a.H, true);
+        const float gx = to_grid((qx / qz + 0.0f) / (float)(a.W - 1)), gy = to_grid((qy / qz + 0.0f) / (float)(a.H - 1));
+        const Lerp ax = axis(gx, a.W, true), ay = axis(gy, a.H, true);
         // pixel indices (view included: the V maps of a source are one array) of the two rows at x0, and the step to x1 (0 at the clamped border)
         const unsigned i00 = (unsigned)((vi * a.H + ay.i0) * a.W + ax.i0), i10 = (unsigned)((vi * a.H + ay.i1) * a.W + ax.i0);
         const unsigned dx = (unsigned)(ax.i1 - ax.i0);
@@ -313,12 +314,7 @@ int launch_gather_cl(const ucnerf_render_params* p, float* feats, int tiled, flo
     const long long M = (long long)p->n * p->S;
     UCNERF_REQUIRE(M < (1ll << 31), "gather_cl: %lld samples in one pass (limit 2^31 - 1)", M);
     a.M = (unsigned)M;
-    {   // magic for idx / S: l = ceil(log2 S), m = ceil(2^(31+l) / S) < 2^32, exact for idx < 2^31
-        unsigned l = 1;
-        while ((1u << l) < (unsigned)p->S) ++l;
-        a.div_m = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)p->S - 1) / (unsigned)p->S);
-        a.div_sh = l - 1;
-    }
+    a.by_S = ExactDiv((unsigned)p->S);
     const dim3 grid(cdiv(M, 256), tiled ? 4 + a.V : 1), block(256);
     if (p->cl.bf16) {
         if (tiled && !given) hipLaunchKernelGGL((feat_gather_cl_kernel<true, false, true>), grid, block, 0, st, a);

@@ -2,38 +2,9 @@
 // stand-alone gather kernels (gather_cl.hip) and the gather fused into the bf16x3 MLP kernel (mlp_bf16.hip, row f1).
 #pragma once
 #include <hip/hip_runtime.h>
-
+#include "geometry_device.h"
 
 namespace ucnerf {
-
-__device__ __forceinline__ float unnorm_cl(float g, int size, bool align) {
-    float i = align ? (g + 1.f) / 2.f * (float)(size - 1) : ((g + 1.f) * (float)size - 1.f) / 2.f;
-    return fminf(fmaxf(i, 0.f), (float)(size - 1));
-}
-
-struct LerpCl { int i0, i1; float w0, w1; };
-
-__device__ __forceinline__ LerpCl axis_cl(float g, int size, bool align) {
-    const float x = unnorm_cl(g, size, align);
-    const float f = floorf(x);
-    LerpCl a;
-    a.i0 = (int)f;
-    a.w1 = x - f;
-    a.w0 = 1.f - a.w1;
-    a.i1 = a.i0 + 1;
-    if (a.i1 > size - 1) { a.i1 = size - 1; a.w1 = 0.f; }
-    return a;
-}
-
-__device__ __forceinline__ void project_cl(const float* M, const float* K, float x, float y, float z, float* qx, float* qy, float* qz) {
-    const float cx = x * M[0] + y * M[1] + z * M[2] + M[3];
-    const float cy = x * M[4] + y * M[5] + z * M[6] + M[7];
-    float cz = x * M[8] + y * M[9] + z * M[10] + M[11];
-    if (fabsf(cz) < 1e-4f) cz = 1e-4f;
-    *qx = cx * K[0] + cy * K[1] + cz * K[2];
-    *qy = cx * K[3] + cy * K[4] + cz * K[5];
-    *qz = cx * K[6] + cy * K[7] + cz * K[8];
-}
 
 typedef float gf2 __attribute__((ext_vector_type(2)));
 

@@ -40,7 +40,8 @@ struct FusedGather {
     float w2c_ref[12], K_ref[9];
     const float* w2cs;
     const float* Ks;
-    unsigned div_m, div_sh;
+    unsigned div_m, div_sh;    // ExactDiv(S), as two plain fields with the divide written out at its four sites in mlp_bf16.hip: an ExactDiv
+                               // member with quot() changes the code of the fused kernels (profiles/geometry_header.md)
     // COORDS instantiation: coordinates GIVEN by the caller (what rendering() of the reference receives from build_rays / build_rays_test,
     // network/renderer.py:215-255) instead of derived from (ray, depth): world points, the three stage copies, the encoded copy -- [M,3] each
     const float* pts_in;

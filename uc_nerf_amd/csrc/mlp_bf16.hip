@@ -633,7 +633,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
             const float zn = COORDS ? gcs[unit == 2 ? 5 : 2] : (qz - nk) / (fk - nk);
             // (wave-uniform sizes pass through an empty asm: their float forms are otherwise hoisted out of the tile loop into vector registers and spilled)
             const int D = unit == 2 ? sopaque(fg.vol_d[2], so_) : fg.vol_d[unit], hh = unit == 2 ? sopaque(fg.vol_h[2], so_) : fg.vol_h[unit], ww = unit == 2 ? sopaque(fg.vol_w[2], so_) : fg.vol_w[unit];
-            const LerpCl ax = axis_cl(u * 2.f - 1.0f, ww, false), ay = axis_cl(v * 2.f - 1.0f, hh, false), az = axis_cl(zn * 2.f - 1.0f, D, false);
+            const Lerp ax = axis(u * 2.f - 1.0f, ww, false), ay = axis(v * 2.f - 1.0f, hh, false), az = axis(zn * 2.f - 1.0f, D, false);
             const unsigned vb = c0;                          // (offsets inside the lane's own volume: fg.vol[hl] in the first sweep, fg.vol[2] in the second)
             VolFp f;
             f.o[0] = vb + (unsigned)((az.i0 * hh + ay.i0) * ww + ax.i0) * VOXB; f.o[1] = vb + (unsigned)((az.i0 * hh + ay.i1) * ww + ax.i0) * VOXB;
@@ -647,7 +647,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         if (part == 2) {
             fb3 = vol_fp(2, (VOXB / 2) * hl, gnf[2], gnf[3]);
             const float u = COORDS ? gcs[3] : npx[0], v = COORDS ? gcs[4] : npx[1];                           // confidence: the stage-3 grid
-            const LerpCl ax = axis_cl(u * 2.f - 1.0f, gW, false), ay = axis_cl(v * 2.f - 1.0f, gH, false);
+            const Lerp ax = axis(u * 2.f - 1.0f, gW, false), ay = axis(v * 2.f - 1.0f, gH, false);
             co[0] = (unsigned)(ay.i0 * gW + ax.i0); co[1] = (unsigned)(ay.i0 * gW + ax.i1);
             co[2] = (unsigned)(ay.i1 * gW + ax.i0); co[3] = (unsigned)(ay.i1 * gW + ax.i1);
             cw[0] = ay.w0 * ax.w0; cw[1] = ay.w0 * ax.w1; cw[2] = ay.w1 * ax.w0; cw[3] = ay.w1 * ax.w1;
@@ -660,7 +660,7 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
             float qx, qy, qv;
             project_cl(mt, mt + 12, x, y, w, &qx, &qy, &qv);
             const float gx = (qx / qv + 0.0f) / (float)(gW - 1) * 2.0f - 1.0f, gy = (qy / qv + 0.0f) / (float)(gH - 1) * 2.0f - 1.0f;
-            const LerpCl ax = axis_cl(gx, gW, true), ay = axis_cl(gy, gH, true);
+            const Lerp ax = axis(gx, gW, true), ay = axis(gy, gH, true);
             fi[pr].p00 = (unsigned)((vi * gH + ay.i0) * gW + ax.i0); fi[pr].p10 = (unsigned)((vi * gH + ay.i1) * gW + ax.i0);
             fi[pr].dx = (unsigned)(ax.i1 - ax.i0);
             fi[pr].w00 = ay.w0 * ax.w0; fi[pr].w01 = ay.w0 * ax.w1; fi[pr].w10 = ay.w1 * ax.w0; fi[pr].w11 = ay.w1 * ax.w1;

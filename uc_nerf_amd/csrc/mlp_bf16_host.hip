@@ -284,12 +284,8 @@ int launch_mlp_fwd_bf16x3_gather(const ucnerf_render_params* rp, const float* di
         f.gen_perturb = gs->perturb; f.gen_lindisp = gs->lindisp;
         f.gen_rays_d = gr->rays_d; f.gen_z = gs->z; f.gen_angle = gr->angle;      // (`dirs` is not read: every lane derives its ray's feature itself)
     }
-    {   // magic for idx / S (gather_cl.hip)
-        unsigned l = 1;
-        while ((1u << l) < (unsigned)rp->S) ++l;
-        f.div_m = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)rp->S - 1) / (unsigned)rp->S);
-        f.div_sh = l - 1;
-    }
+    const ExactDiv by_S((unsigned)rp->S);
+    f.div_m = by_S.m; f.div_sh = by_S.sh;
     if (tail_c) {
         const int cus = device_cus();
         if (cus <= 0) return fail(UCNERF_EHIP, "mlp_fwd: no device");

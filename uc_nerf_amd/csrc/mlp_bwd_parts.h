@@ -26,7 +26,7 @@ struct WgPair {
     int ldg, nout, ldx, w, xdiv, ldw, split, cost;
     int xmode;
     int xtile_f;                          // xmode 2: X lives in the MLP tile layout [m / 32][xtile_f][32] (X points at its first column's row): ldx unused
-    unsigned div_m, div_sh;               // s / xdiv = __umulhi(s, div_m) >> div_sh
+    ExactDiv by_xdiv;                     // s / xdiv = by_xdiv.quot(s) where xdiv >= 2
 };
 struct WgArgs {
     WgPair p[WG_MAX_PAIRS];

@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(WG_THREADS, 3) mlp_wgrad_kernel(WgArgs a WG_ST
                     for (int e = 0; e < 8; ++e) {
                         const int s = stg * WG_STAGE + 8 * oct + e;
                         const unsigned sc = (unsigned)(s < wg_m ? s : wg_m - 1);
-                        off[e] = ((sc & one) | ((__umulhi(sc, q.div_m) >> q.div_sh) & ~one)) * ld + gc;
+                        off[e] = ((sc & one) | (q.by_xdiv.quot(sc) & ~one)) * ld + gc;
                     }
                 }
             }
@@ -485,12 +485,7 @@ int wgrad_add(WgArgs* a, const void* G, int ldg_bytes, int nout, const void* X, 
     q.split = gW_hi || gb_hi ? split : 1 << 30;
     q.xtile_f = xtile_f;
     if (xtile_f > 0 && (xdiv != 1 || x24)) return fail(UCNERF_EINVAL, "mlp_bwd: a tiled weight-gradient operand is fp32 with one row per sample");
-    {   // magic numbers for s / xdiv (s < 2^31): __umulhi(s, div_m) >> div_sh
-        unsigned l = 1;
-        while ((1u << l) < (unsigned)xdiv) ++l;
-        q.div_m = (unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)xdiv - 1) / (unsigned)xdiv);
-        q.div_sh = l - 1;
-    }
+    q.by_xdiv = ExactDiv((unsigned)xdiv);
     // ~ bytes moved per stage (a 24-bit column weighs 3/4 of an fp32 one) + a fixed part (a stage is mostly latency: measured, weighting by bytes
     //   alone left the blocks of the narrow pairs running 1.5x longer than the rest)
     q.cost = ((nout + 31) & ~31) * 3 / 4 + ((wd + 31) & ~31) * (x24 ? 3 : 4) / 4 + 224;

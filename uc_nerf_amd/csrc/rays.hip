@@ -2,6 +2,7 @@
 #include "common.h"
 #include "sincos_cw.h"
 #include "raygen_device.h"
+#include "geometry_device.h"
 
 #include <atomic>
 #include <climits>
@@ -268,13 +269,8 @@ __device__ __forceinline__ void cascade_ray(const Params& p, int r, float x, flo
         p.z[o1] = z;
         const float x = ox + z * wx, y = oy + z * wy, w = oz + z * wz;
         p.pts[o] = x; p.pts[o + 1] = y; p.pts[o + 2] = w;
-        const float cx = x * M[0] + y * M[1] + w * M[2] + M[3];      // utils/utils.py:333-367
-        const float cy = x * M[4] + y * M[5] + w * M[6] + M[7];
-        float cz = x * M[8] + y * M[9] + w * M[10] + M[11];
-        if (fabsf(cz) < 1e-4f) cz = 1e-4f;
-        const float qx = cx * K[0] + cy * K[1] + cz * K[2];
-        const float qy = cx * K[3] + cy * K[4] + cz * K[5];
-        const float qz = cx * K[6] + cy * K[7] + cz * K[8];
+        float qx, qy, qz;
+        project(M, K, x, y, w, &qx, &qy, &qz);                         // utils/utils.py:333-367
         const float u = (qx / qz + 0.0f) / inv_w, v = (qy / qz + 0.0f) / inv_h;
         p.ndc1[o] = u; p.ndc1[o + 1] = v; p.ndc1[o + 2] = (qz - nf[0]) / (nf[1] - nf[0]);
         p.ndc2[o] = u; p.ndc2[o + 1] = v; p.ndc2[o + 2] = (qz - nf[2]) / (nf[3] - nf[2]);
@@ -330,18 +326,9 @@ __global__ void ndc_project_kernel(ucnerf_ndc_project_params p) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.m) return;
     float x = p.pts[3 * (size_t)i], y = p.pts[3 * (size_t)i + 1], z = p.pts[3 * (size_t)i + 2];
-    if (p.has_w2c) {
-        const float* M = p.w2c;
-        float cx = x * M[0] + y * M[1] + z * M[2] + M[3];
-        float cy = x * M[4] + y * M[5] + z * M[6] + M[7];
-        float cz = x * M[8] + y * M[9] + z * M[10] + M[11];
-        if (fabsf(cz) < 1e-4f) cz = 1e-4f;
-        x = cx; y = cy; z = cz;
-    }
-    const float* K = p.K;
-    float qx = x * K[0] + y * K[1] + z * K[2];
-    float qy = x * K[3] + y * K[4] + z * K[5];
-    float qz = x * K[6] + y * K[7] + z * K[8];
+    if (p.has_w2c) to_camera(p.w2c, x, y, z, &x, &y, &z);
+    float qx, qy, qz;
+    apply_intrinsics(p.K, x, y, z, &qx, &qy, &qz);
     float u = (qx / qz + 0.0f) / p.inv_scale[0];
     float v = (qy / qz + 0.0f) / p.inv_scale[1];
     size_t o = 3 * (size_t)i;

@@ -7,6 +7,7 @@
 #include <mutex>
 #include "mlp_layout.h"
 #include "mlp_bf16.h"
+#include "geometry_device.h"
 
 namespace ucnerf {
 
@@ -37,15 +38,8 @@ __global__ void __launch_bounds__(256) render_points_kernel(PointsArgs a) {
                 w = a.rays_o[2] + z * a.rays_d[3 * r + 2];
     const size_t o = 3 * (size_t)idx;
     a.pts[o] = x; a.pts[o + 1] = y; a.pts[o + 2] = w;
-    const float* M = a.w2c;
-    const float cx = x * M[0] + y * M[1] + w * M[2] + M[3];
-    const float cy = x * M[4] + y * M[5] + w * M[6] + M[7];
-    float cz = x * M[8] + y * M[9] + w * M[10] + M[11];
-    if (fabsf(cz) < 1e-4f) cz = 1e-4f;
-    const float* K = a.K;
-    const float qx = cx * K[0] + cy * K[1] + cz * K[2];
-    const float qy = cx * K[3] + cy * K[4] + cz * K[5];
-    const float qz = cx * K[6] + cy * K[7] + cz * K[8];
+    float qx, qy, qz;
+    project(a.w2c, a.K, x, y, w, &qx, &qy, &qz);
     const float u = (qx / qz + 0.0f) / a.inv_w, v = (qy / qz + 0.0f) / a.inv_h;
     float n1 = a.near, f1 = a.far, n2 = a.near, f2 = a.far, n3 = a.near, f3 = a.far;
     if (a.near_far) {
