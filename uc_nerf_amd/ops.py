@@ -625,26 +625,58 @@ def feat_gather_fwd(src, pts, ndc1, ndc2, ndc3, tiled=False, u_out=None):
     return feats if tiled else feats.view(*lead.shape[:-1], src.F)
 
 
-def feat_gather_bwd(src, pts, ndc1, ndc2, ndc3, g_feats, need=(True, True, True, True, True)):
-    """Returns grads (g_vol1, g_vol2, g_vol3, g_conf, g_img_feat); entries not needed are None."""
+# route of ucnerf_feat_gather_bwd -> (volumes accumulated channel-last in the caller's arrays, image features likewise)
+GATHER_BWD_ROUTES = {"scratch": (False, False), "direct": (False, False), "cl": (True, True), "cl_vols": (True, False), "cl_img_feat": (False, True)}
+
+
+def feat_gather_bwd(src, pts, ndc1, ndc2, ndc3, g_feats, need=(True, True, True, True, True), route="scratch"):
+    """Returns grads (g_vol1, g_vol2, g_vol3, g_conf, g_img_feat); entries not needed are None.
+    route: which of the entry point's routes runs (include/ucnerf_hip.h, ucnerf_feat_gather_bwd):
+      "scratch"      channel-last accumulation in a scratch buffer, then one transposing add (the default);
+      "direct"       no scratch buffer: one atomic per corner and channel, straight into the channel-major arrays;
+      "cl"           every source's gradient accumulated in a channel-last array of its own (g_cl), as RenderPass.backward does for sources read
+                     in place; the gradients come back in the sources' shapes with channel-last strides.  The only route that serves
+                     in-place sources;
+      "cl_vols" / "cl_img_feat"   g_cl for the volumes / the image features alone, the other through the scratch buffer."""
+    if route not in GATHER_BWD_ROUTES:
+        raise ValueError("uc_nerf_amd.feat_gather_bwd: route must be one of %s, got %r" % (sorted(GATHER_BWD_ROUTES), route))
+    cl_vol, cl_feat = GATHER_BWD_ROUTES[route]
+    if (any(src.inplace[:3]) and not cl_vol) or (src.inplace[3] and not cl_feat):
+        raise RuntimeError("uc_nerf_amd.feat_gather_bwd: channel-last sources take their gradients channel-last (route='cl')")
+
+    def cl_zeros(t, perm):          # zeros of t's shape whose memory is channel-last (16-byte aligned: a fresh allocation)
+        return torch.zeros([t.shape[i] for i in perm], device=t.device).permute([perm.index(i) for i in range(len(perm))])
+
+    gv = [None if not (need[k] and v is not None) else cl_zeros(v, (1, 2, 3, 0)) if cl_vol else torch.zeros(v.shape, device=v.device)
+          for k, v in enumerate(src.vols)]
+    gc = torch.zeros_like(src.conf) if (need[3] and src.conf is not None) else None
+    gi = None
+    if need[4] and src.imgs is not None:
+        gi = cl_zeros(src.img_feat, (0, 2, 3, 1)) if cl_feat else torch.zeros(src.img_feat.shape, device=src.img_feat.device)
+    _feat_gather_bwd_into(src, pts, ndc1, ndc2, ndc3, g_feats, (gv[0], gv[1], gv[2], gc, gi), route)
+    return gv[0], gv[1], gv[2], gc, gi
+
+
+def _feat_gather_bwd_into(src, pts, ndc1, ndc2, ndc3, g_feats, grads, route):
+    """One call of ucnerf_feat_gather_bwd ACCUMULATING into `grads` (what feat_gather_bwd returned for the same sources and route)."""
     pts, ndc1, ndc2, ndc3, g_feats = _opt(pts), _opt(ndc1), _opt(ndc2), _opt(ndc3), _f32(g_feats)
     lead = next(t for t in (pts, ndc1, ndc3) if t is not None)
-    if any(src.inplace):
-        raise RuntimeError("uc_nerf_amd.feat_gather_bwd: channel-last sources are served by the render passes (RenderPass.backward)")
+    cl_vol, cl_feat = GATHER_BWD_ROUTES[route]
     bp = L.FeatGatherBwdParams()
     src.fill(bp.fwd)
     bp.fwd.m = lead.numel() // 3
     bp.fwd.pts, bp.fwd.ndc1, bp.fwd.ndc2, bp.fwd.ndc3 = _ptr(pts), _ptr(ndc1), _ptr(ndc2), _ptr(ndc3)
     bp.g_feats = _ptr(g_feats)
-    gv = [torch.zeros_like(v) if (need[k] and v is not None) else None for k, v in enumerate(src.vols)]
-    gc = torch.zeros_like(src.conf) if (need[3] and src.conf is not None) else None
-    gi = torch.zeros_like(src.img_feat) if (need[4] and src.imgs is not None) else None
+    gv, gc, gi = grads[:3], grads[3], grads[4]
     for k in range(3):
-        bp.g_vol[k] = _ptr(gv[k])
-    bp.g_conf, bp.g_img_feat = _ptr(gc), _ptr(gi)
-    bp.scratch = _ptr(_gather_scratch(src, bp.fwd, lead.device))
+        bp.g_vol[k] = None if cl_vol else _ptr(gv[k])
+        bp.g_cl.vol[k] = _ptr(gv[k]) if cl_vol else None
+    bp.g_conf = _ptr(gc)
+    bp.g_img_feat = None if cl_feat else _ptr(gi)
+    bp.g_cl.img_feat = _ptr(gi) if cl_feat else None
+    via_scratch = (not cl_vol and any(g is not None for g in gv)) or (not cl_feat and gi is not None)
+    bp.scratch = _ptr(_gather_scratch(src, bp.fwd, lead.device)) if (route == "scratch" or (via_scratch and route != "direct")) else None
     _launch("ucnerf_feat_gather_bwd", bp, lead.device)
-    return gv[0], gv[1], gv[2], gc, gi
 
 
 def _gather_scratch(src, fwd_params, device):
