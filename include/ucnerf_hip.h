@@ -59,6 +59,11 @@ int32_t ucnerf_fused_tail_fits(int32_t n, int32_t S);
  * that pass (size AND the re-sampling limits: S - 1 <= 128 bins, S + n_samples <= 512), so that a host that folds the ray generation into the
  * pass exactly when it takes the tail route decides as the library does (round 4's advisor finding). */
 int32_t ucnerf_fused_tail_fits_resample(int32_t n, int32_t S, int32_t n_samples);
+/* Should a fine pass of n rays take its n_coarse coarse depths' network outputs from the coarse pass and evaluate the n_fine new depths only
+ * (ucnerf_composite_merged_fwd composites the two row sets)?  1, except where the pass over all n_coarse + n_fine depths is of the size that
+ * takes the tail route above: that pass is one launch already, and the reuse would put a compositing launch back behind it.  Like
+ * ucnerf_fused_tail_fits it speaks of the size alone; with the tail route switched off it is 1 at every size. */
+int32_t ucnerf_reuse_coarse_pays(int32_t n, int32_t n_coarse, int32_t n_fine);
 /* Digest of the sources, headers and flags this binary was linked from (uc_nerf_amd/build.py: source_hash()): a host can tell a library
  * that does not belong to the tree it sits in (tests/test_abi_host.py), and __graft_entry__.build() rebuilds one that was not linked on
  * the machine it runs on. */
@@ -565,6 +570,35 @@ typedef struct {
 } ucnerf_merge_rows_params;
 int ucnerf_merge_rows(const ucnerf_merge_rows_params* p, void* stream);
 
+/* a9 over the rows of a sorted merge, read where they are (added to ABI v6; nothing above moved): what ucnerf_merge_rows into out [n,na+nb,4]
+ * followed by ucnerf_composite_fwd (live variant) on `out` and `z` produces, bit for bit, from ONE launch and with no merged array written or
+ * read back.  The wave that composites a ray inverts the ray's rank row in LDS (inv[rank[j]] = j for j in cat(a, b) order) and fetches merged
+ * position i from row inv[i] of raw_a or raw_b; lane split, scan, reduction order and arithmetic are those of ucnerf_composite_fwd.
+ * The hierarchical renderer's fine pass (data/ray_utils.py:199-224) with the network evaluated on the new depths only: raw_a = their outputs,
+ * raw_b = the coarse pass's, rank = ucnerf_sample_pdf_params.merge_rank, z = its z_sorted.
+ * 1 <= na + nb <= 1024, na >= 0, nb >= 0; raw_a / raw_b 16-byte aligned (either may be NULL when its row count is 0).  `rank` must hold a
+ * permutation of 0 .. na+nb-1 per ray: the producer guarantees it and it is NOT checked (any other contents give undefined outputs, never an
+ * access outside the arrays named here).
+ * (Declared with a struct tag, like ucnerf_depth_hypotheses_params: mirrored in _lib.ADDED_STRUCTS.) */
+struct ucnerf_composite_merged_params {
+    int32_t n, na, nb;         /* rays; rows per ray in raw_a / raw_b */
+    int32_t white_bkgd;
+    const float* raw_a;        /* [n,na,4] rows of the first na elements of the concatenation */
+    const float* raw_b;        /* [n,nb,4] */
+    const int32_t* rank;       /* [n,na+nb]: position in z of element j of cat(a, b) */
+    const float* z;            /* [n,na+nb] the sorted merged depths */
+    float* rgb_map;            /* [n,3] */
+    float* depth_map;          /* [n] */
+    float* acc_map;            /* [n] or NULL */
+    float* disp_map;           /* [n] or NULL */
+    float* weights;            /* [n,na+nb] or NULL, in merged order */
+    float* var;                /* [n] or NULL (needs na + nb >= 2) */
+    const float* u;            /* optional [n,na+nb] per-sample uncertainty in merged order ... */
+    float* wu;                 /* ... and [n] out: sum_i w_i u_i */
+};
+typedef struct ucnerf_composite_merged_params ucnerf_composite_merged_params;
+int ucnerf_composite_merged_fwd(const ucnerf_composite_merged_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * f2   the step in front of the path: cost-volume assembly and depth regression of one cascade stage.
  *      ucnerf_cost_volume replaces the loop of network/mvs_models.py:609-626: homo_warp (utils/utils.py:1105-1172,
@@ -692,7 +726,8 @@ typedef struct {
     float* workspace;
     /* outputs */
     float* rgb_map;            /* [n,3] */
-    float* depth_map;          /* [n] */
+    float* depth_map;          /* [n]   (rgb_map and depth_map both NULL, raw given: the pass evaluates the network into raw and composites
+                                  nothing -- no compositing launch, no other output; for rows composited by ucnerf_composite_merged_fwd) */
     float* acc_map;            /* [n] or NULL */
     float* weights;            /* [n,S] or NULL */
     float* var;                /* [n] or NULL */

@@ -117,6 +117,11 @@ class MergeRowsParams(C.Structure):
     _fields_ = [("n", i32), ("na", i32), ("nb", i32), ("width", i32), ("a", vp), ("b", vp), ("rank", vp), ("out", vp)]
 
 
+class CompositeMergedParams(C.Structure):
+    _fields_ = [("n", i32), ("na", i32), ("nb", i32), ("white_bkgd", i32), ("raw_a", vp), ("raw_b", vp), ("rank", vp), ("z", vp), ("rgb_map", vp),
+                ("depth_map", vp), ("acc_map", vp), ("disp_map", vp), ("weights", vp), ("var", vp), ("u", vp), ("wu", vp)]
+
+
 class CostVolumeParams(C.Structure):
     _fields_ = [("V", i32), ("C", i32), ("H", i32), ("W", i32), ("D", i32), ("pad", i32), ("feats", vp), ("proj", vp),
                 ("depth_values", vp), ("variance", vp), ("count", vp)]
@@ -184,7 +189,8 @@ STRUCTS = {
 
 # structs added to ABI v6 after its struct table was fixed (STRUCTS above is that table, kept as it was: additive entry points move nothing in it);
 # checked against the library's sizeof() at load time like the others
-ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams}
+ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams,
+                 "ucnerf_composite_merged_params": CompositeMergedParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -198,6 +204,7 @@ SYMBOLS = {
     "ucnerf_set_fused_tail": (C.c_int32, [C.c_int32]),
     "ucnerf_fused_tail_fits": (C.c_int32, [C.c_int32, C.c_int32]),
     "ucnerf_fused_tail_fits_resample": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "ucnerf_reuse_coarse_pays": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_source_hash": (C.c_char_p, []),
     "ucnerf_event_create": (C.c_void_p, []),
     "ucnerf_event_record": (C.c_int, [_P, _P]),
@@ -241,6 +248,7 @@ SYMBOLS = {
     "ucnerf_sample_pdf": (C.c_int, [_P, _P]),
     "ucnerf_composite_sample_pdf": (C.c_int, [_P, _P, _P]),
     "ucnerf_merge_rows": (C.c_int, [_P, _P]),
+    "ucnerf_composite_merged_fwd": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),

@@ -18,6 +18,33 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(ucnerf_composite_par
     composite_ray<E, VARIANT>(p, ray, lane, nullptr);
 }
 
+// The same ray from the rows of a sorted merge, read where they are (ucnerf_composite_merged_fwd): the wave first inverts its ray's rank row through
+// LDS -- inv[rank[j]] = j for j in cat(a, b) order, S ints per wave -- then composite_ray fetches merged position i from row inv[i] of a or b.
+template <int E>
+__global__ void __launch_bounds__(256) composite_merged_fwd_kernel(ucnerf_composite_merged_params m) {
+    extern __shared__ int inv_all[];            // [4 waves][S]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ray = blockIdx.x * 4 + wave;
+    const int S = m.na + m.nb;
+    int* inv = inv_all + wave * S;
+    if (ray < m.n) {
+        const int* rank = m.rank + (size_t)ray * S;
+        for (int j = lane; j < S; j += 64) {
+            const unsigned r = (unsigned)rank[j];
+            if (r < (unsigned)S) inv[r] = j;      // (a rank outside the row is dropped: nothing outside this wave's S ints is written)
+        }
+    }
+    __syncthreads();
+    if (ray >= m.n) return;
+    ucnerf_composite_params p;
+    p.n = m.n; p.S = S; p.variant = 0; p.white_bkgd = m.white_bkgd;
+    p.raw = nullptr; p.z = m.z; p.rays_d = nullptr; p.noise = nullptr;
+    p.rgb_map = m.rgb_map; p.depth_map = m.depth_map; p.acc_map = m.acc_map; p.disp_map = m.disp_map;
+    p.weights = m.weights; p.var = m.var; p.u = m.u; p.wu = m.wu;
+    const MergedRows rows{reinterpret_cast<const float4*>(m.raw_a), reinterpret_cast<const float4*>(m.raw_b), m.na, m.nb, inv};
+    composite_ray<E, 0>(p, ray, lane, nullptr, rows);
+}
+
 // Backward of the live variant.  With gw_i = dL/dw_i:
 //   dL/dalpha_i = gw_i T_i - (sum_{k>i} gw_k w_k) / f_i,   dL/dsigma_i = dL/dalpha_i * exp(-sigma_i),
 //   dL/drgb_i = w_i * g_rgb.
@@ -106,6 +133,30 @@ int ucnerf_composite_fwd(const ucnerf_composite_params* p, void* stream) {
     else if (E <= 8) launch_fwd<8>(*p, st);
     else launch_fwd<16>(*p, st);
     return check_launch("composite_fwd");
+}
+
+int ucnerf_composite_merged_fwd(const ucnerf_composite_merged_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "composite_merged_fwd: null params");
+    UCNERF_COUNT(p->n);
+    UCNERF_REQUIRE(p->na >= 0 && p->nb >= 0, "composite_merged_fwd: negative row count (na = %d, nb = %d)", p->na, p->nb);
+    const long long S = (long long)p->na + p->nb;
+    UCNERF_REQUIRE(S >= 1 && S <= 1024, "composite_merged_fwd: na + nb = %lld outside 1..1024", S);
+    UCNERF_REQUIRE((p->raw_a || p->na == 0) && (p->raw_b || p->nb == 0) && p->rank && p->z && p->rgb_map && p->depth_map, "composite_merged_fwd: null pointer");
+    UCNERF_REQUIRE(!p->var || S >= 2, "composite_merged_fwd: var needs na + nb >= 2");
+    UCNERF_REQUIRE((((uintptr_t)p->raw_a | (uintptr_t)p->raw_b) & 15) == 0, "composite_merged_fwd: raw_a and raw_b must be 16-byte aligned");
+    UCNERF_REQUIRE(((uintptr_t)p->rank & 3) == 0, "composite_merged_fwd: rank must be 4-byte aligned");
+    UCNERF_REQUIRE(!p->wu || p->u, "composite_merged_fwd: wu (sum of w*u) needs the per-sample uncertainty u");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(cdiv(p->n, 4)), block(256);
+    const size_t lds = 4 * (size_t)S * sizeof(int);      // one inverse per wave: at most 16 KB
+    const int E = composite_lane_samples((int)S);        // the lane split of ucnerf_composite_fwd at this S: same weights, bit for bit
+    if (E <= 1) hipLaunchKernelGGL(composite_merged_fwd_kernel<1>, grid, block, lds, st, *p);
+    else if (E <= 2) hipLaunchKernelGGL(composite_merged_fwd_kernel<2>, grid, block, lds, st, *p);
+    else if (E <= 3) hipLaunchKernelGGL(composite_merged_fwd_kernel<3>, grid, block, lds, st, *p);
+    else if (E <= 4) hipLaunchKernelGGL(composite_merged_fwd_kernel<4>, grid, block, lds, st, *p);
+    else if (E <= 8) hipLaunchKernelGGL(composite_merged_fwd_kernel<8>, grid, block, lds, st, *p);
+    else hipLaunchKernelGGL(composite_merged_fwd_kernel<16>, grid, block, lds, st, *p);
+    return check_launch("composite_merged_fwd");
 }
 
 int ucnerf_composite_bwd(const ucnerf_composite_bwd_params* bp, void* stream) {

@@ -37,12 +37,33 @@ struct Sample {
     float r, g, b, alpha, f, ex;   // activated colour, alpha, transmittance factor (1 - alpha + 1e-10), exp(-sigma)
 };
 
+// where a ray's raw rows [.,4] come from: Rows()(p, ray, i) is row i (i < p.S) of ray `ray`.  DenseRows: the array p.raw [n,S,4]
+struct DenseRows {
+    __device__ __forceinline__ float4 operator()(const ucnerf_composite_params& p, int ray, int i) const {
+        return reinterpret_cast<const float4*>(p.raw)[(size_t)ray * p.S + i];
+    }
+};
+
+// Rows of a sorted merge read in place (ucnerf_composite_merged_fwd): merged position i of the ray is row inv[i] of cat(a[ray], b[ray]); `inv`
+// is the wave's own inverse of the ray's merge_rank row, in LDS.  p.raw is not read.  (The index is clamped to the rows there are: memory-safe
+// for any rank contents.)
+struct MergedRows {
+    const float4* a;        // [n,na] rows of the first na elements of the concatenation
+    const float4* b;        // [n,nb]
+    int na, nb;
+    const int* inv;         // [na+nb]
+    __device__ __forceinline__ float4 operator()(const ucnerf_composite_params& p, int ray, int i) const {
+        const int j = min((unsigned)inv[i], (unsigned)(na + nb - 1));
+        return j < na ? a[(size_t)ray * na + j] : b[(size_t)ray * nb + (j - na)];
+    }
+};
+
 // loads sample i of ray `ray` and applies the variant's activations; i >= S gives a neutral sample
-template <int VARIANT>
-__device__ __forceinline__ Sample load_sample(const ucnerf_composite_params& p, int ray, int i, float dnorm) {
+template <int VARIANT, class Rows>
+__device__ __forceinline__ Sample load_sample(const ucnerf_composite_params& p, int ray, int i, float dnorm, const Rows& rows) {
     Sample s;
     if (i >= p.S) { s.r = s.g = s.b = s.alpha = s.ex = 0.f; s.f = 1.f; return s; }
-    const float4 raw = reinterpret_cast<const float4*>(p.raw)[(size_t)ray * p.S + i];
+    const float4 raw = rows(p, ray, i);
     if (VARIANT == 0) {                       // renderer.py:29: alpha = 1 - exp(-sigma)
         s.r = raw.x; s.g = raw.y; s.b = raw.z;
         s.ex = expf(-raw.w);
@@ -59,10 +80,16 @@ __device__ __forceinline__ Sample load_sample(const ucnerf_composite_params& p, 
     return s;
 }
 
+template <int VARIANT>
+__device__ __forceinline__ Sample load_sample(const ucnerf_composite_params& p, int ray, int i, float dnorm) {
+    return load_sample<VARIANT>(p, ray, i, dnorm, DenseRows());
+}
+
 // Forward of one ray by one 64-lane wave: lane l owns samples [l*E, (l+1)*E).  Writes the ray's outputs named in `p`; `w_keep` (optional,
-// any address space through a generic pointer) receives the S weights as well -- the fused re-sampling reads them from LDS.
-template <int E, int VARIANT>
-__device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, int ray, int lane, float* w_keep) {
+// any address space through a generic pointer) receives the S weights as well -- the fused re-sampling reads them from LDS.  `rows`: where the
+// raw rows are read from (above); everything behind the load is the one body every compositing launch runs.
+template <int E, int VARIANT, class Rows>
+__device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, int ray, int lane, float* w_keep, const Rows& rows) {
     float dnorm = 0.f;
     if (VARIANT == 1) {
         const float* d = p.rays_d + 3 * (size_t)ray;
@@ -73,7 +100,7 @@ __device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, 
     float prod = 1.f;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-        sm[e] = load_sample<VARIANT>(p, ray, lane * E + e, dnorm);
+        sm[e] = load_sample<VARIANT>(p, ray, lane * E + e, dnorm, rows);
         T[e] = prod;
         prod *= sm[e].f;
     }
@@ -116,6 +143,11 @@ __device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, 
         if (p.var) p.var[ray] = var;
         if (p.wu) p.wu[ray] = su;
     }
+}
+
+template <int E, int VARIANT>
+__device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, int ray, int lane, float* w_keep) {
+    composite_ray<E, VARIANT>(p, ray, lane, w_keep, DenseRows());
 }
 
 // E (samples per lane) the launchers instantiate for S samples per ray: the association order of the transmittance products depends on it,

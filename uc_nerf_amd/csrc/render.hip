@@ -184,6 +184,9 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
     float* raw_fused = nullptr;
     ucnerf_composite_params c;
     ucnerf_sample_pdf_params s_res;
+    // evaluation only (no rgb_map, no depth_map): the pass ends with the network's outputs in p->raw -- no compositing, in a launch of its own or in
+    // the gather-fused launch's tail.  A caller that composites the rows together with another pass's (ucnerf_composite_merged_fwd) asks for this.
+    const bool eval_only = !p->rgb_map;
     if (p->resample) {                                   // ABI v4: this pass's compositing and the next pass's depths from ONE launch
         UCNERF_REQUIRE(!p->u_sampled, "render_fused_fwd: resample and the per-sample uncertainty outputs exclude each other");
         s_res = *p->resample;
@@ -199,7 +202,7 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
                        "render_fused_fwd: precision 3 (gather fused into the MLP kernel) needs the channel-last sources; it keeps no features "
                        "and returns no per-sample uncertainty");
         const bool gen = p->gen_rays != nullptr;          // rays, depths and direction features are generated inside the launch (w->angle: its per-sample scratch)
-        const bool tail = tail_fits(p, p->resample ? &s_res : nullptr);
+        const bool tail = !eval_only && tail_fits(p, p->resample ? &s_res : nullptr);
         // the view-direction features: given (dir_feat), generated with the rays (gen), made in the tail route's block prologues when the rotation
         // lives on the device (w2c_dir_dev: no launch of its own), or from ucnerf_dir_feature
         const bool dirs_in_tail = tail && !gen && !p->dir_feat && p->w2c_dir_dev;
@@ -242,6 +245,7 @@ static int run_forward(const ucnerf_render_params* p, hipStream_t st, Workspace*
         if (p->ev_mlp_stop && !replay && (rc = ucnerf_event_record(p->ev_mlp_stop, st))) return rc;
     }
 
+    if (eval_only) return UCNERF_OK;
     composite_args(p, m.raw, &c);
     if (p->resample) return ucnerf_composite_sample_pdf(&c, &s_res, st);
     return ucnerf_composite_fwd(&c, st);
@@ -257,6 +261,13 @@ int64_t ucnerf_fused_tail_launches(void) { return (int64_t)g_tail_launches.load(
 int32_t ucnerf_set_fused_tail(int32_t on) { tail_knobs_init(); return g_tail_on.exchange(on ? 1 : 0); }
 int32_t ucnerf_fused_tail_fits(int32_t n, int32_t S) { return tail_size_fits(n, S) ? 1 : 0; }
 int32_t ucnerf_fused_tail_fits_resample(int32_t n, int32_t S, int32_t n_samples) { return tail_size_fits(n, S) && tail_resample_fits(S, n_samples, 0) ? 1 : 0; }
+// A fine pass over all n_coarse + n_fine depths that is of the tail route's size is ONE launch, compositing included; taking the coarse rows from
+// the coarse pass instead puts a compositing launch back behind a network launch that is one round of tiles shorter at best (at most three to
+// begin with).  Such passes evaluate all depths (profiles/reuse_default.md has the 512-ray measurement); every larger one reuses.
+int32_t ucnerf_reuse_coarse_pays(int32_t n, int32_t n_coarse, int32_t n_fine) {
+    if (n < 1 || n_coarse < 1 || n_fine < 1) return 0;
+    return tail_size_fits(n, n_coarse + n_fine) ? 0 : 1;
+}
 
 int64_t ucnerf_render_workspace_floats(int32_t n, int32_t S, int32_t V) {
     if (n < 0 || S < 1 || V < 1 || V > 8) return fail(UCNERF_EINVAL, "render_workspace: bad sizes n=%d S=%d V=%d", n, S, V);
@@ -323,8 +334,10 @@ int ucnerf_render_fused_bwd(const ucnerf_render_bwd_params* bp, void* stream) {
 int ucnerf_render_fused_fwd(const ucnerf_render_params* p, void* stream) {
     UCNERF_REQUIRE(p, "render_fused_fwd: null params");
     UCNERF_COUNT(p->n);
-    UCNERF_REQUIRE(p->rays_o && p->rays_d && p->z && p->workspace && p->wstream && p->rgb_map && p->depth_map,
+    UCNERF_REQUIRE(p->rays_o && p->rays_d && p->z && p->workspace && p->wstream && (!p->rgb_map == !p->depth_map) && (p->rgb_map || p->raw),
                    "render_fused_fwd: null pointer");
+    UCNERF_REQUIRE(p->rgb_map || !(p->acc_map || p->weights || p->var || p->u_sampled || p->wu_map || p->resample),
+                   "render_fused_fwd: a pass without rgb_map / depth_map evaluates the network into raw only (no compositing outputs, no resample)");
     UCNERF_REQUIRE(p->S >= 1 && p->S <= 1024, "render_fused_fwd: S = %d outside 1..1024", p->S);
     UCNERF_REQUIRE((long long)p->n * p->S < (1ll << 31), "render_fused_fwd: n*S overflows int32");
     UCNERF_REQUIRE(((uintptr_t)p->workspace & 15) == 0, "render_fused_fwd: workspace must be 16-byte aligned");

@@ -1217,6 +1217,36 @@ def merge_rows(a, b, rank):
     return out
 
 
+def composite_merged_fwd(raw_a, raw_b, rank, z, white_bkgd=False, want_var=True, u=None):
+    """composite_fwd(merge_rows(raw_a, raw_b, rank), z, 0, white_bkgd, want_var=want_var, u=u) from one launch, bit for bit, with no merged array:
+    raw_a [n,na,4], raw_b [n,nb,4], rank [n,na+nb] (int32, a permutation per ray: sample_pdf's merge_rank), z [n,na+nb] sorted."""
+    raw_a, raw_b, z = _f32(raw_a, "raw_a"), _f32(raw_b, "raw_b"), _f32(z, "z")
+    n, S = z.shape
+    na, nb = raw_a.shape[1], raw_b.shape[1]
+    if (rank.dtype != torch.int32 or tuple(rank.shape) != (n, S) or tuple(raw_a.shape) != (n, na, 4) or tuple(raw_b.shape) != (n, nb, 4)
+            or na + nb != S or rank.device != z.device):
+        raise RuntimeError("uc_nerf_amd.composite_merged_fwd: shape / dtype mismatch")
+    rank = rank.contiguous()
+    dev = z.device
+    p = L.CompositeMergedParams()
+    p.n, p.na, p.nb, p.white_bkgd = n, na, nb, int(white_bkgd)
+    out = dict(rgb=torch.empty(n, 3, device=dev), depth=torch.empty(n, device=dev), acc=torch.empty(n, device=dev),
+               disp=torch.empty(n, device=dev), weights=torch.empty(n, S, device=dev))
+    if want_var and S >= 2:
+        out["var"] = torch.empty(n, device=dev)
+    p.raw_a, p.raw_b, p.rank, p.z = _ptr(raw_a) if na else None, _ptr(raw_b) if nb else None, _ptr(rank), _ptr(z)
+    p.rgb_map, p.depth_map, p.acc_map, p.disp_map = _ptr(out["rgb"]), _ptr(out["depth"]), _ptr(out["acc"]), _ptr(out["disp"])
+    p.weights, p.var = _ptr(out["weights"]), _ptr(out.get("var"))
+    if u is not None:
+        u = _f32(u, "u")
+        if tuple(u.shape) != (n, S):
+            raise RuntimeError("uc_nerf_amd.composite_merged_fwd: u must be [n,S]")
+        out["wu"] = torch.empty(n, device=dev)
+        p.u, p.wu = _ptr(u), _ptr(out["wu"])
+    _launch("ucnerf_composite_merged_fwd", p, dev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ f2
 def _cost_volume_params(feats, proj, depth_values, pad):
     V, Cc, H, W = feats.shape
@@ -1443,7 +1473,13 @@ class RenderPass:
         values of RaySampler.__call__, bit for bit, with no launch of its own.
         w2c_dir_dev (with dir_feat=None): the rotation of the view-direction feature as a float32 DEVICE tensor ([3,4] or [4,4], contiguous), read by
         the kernels in place of the by-value w2c_dir -- rendering() holds pose_ref['w2cs'][0] on the device; on the tail route the features are
-        then made inside the pass's one launch."""
+        then made inside the pass's one launch.
+        want=None: evaluation only -- the pass ends with the network's outputs in out["raw"] (the only entry) and composites nothing."""
+        eval_only = want is None
+        if eval_only:
+            want, keep = (), ("raw",)
+            if resample is not None:
+                raise RuntimeError("uc_nerf_amd.RenderPass: an evaluation-only pass (want=None) composites nothing and cannot re-sample")
         rays_d, z = _f32(rays_d, "rays_d"), _f32(z, "z")
         dir_feat = _f32(dir_feat, "dir_feat") if dir_feat is not None else None
         n, S = z.shape
@@ -1454,7 +1490,7 @@ class RenderPass:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=dev)
         near_far = _f32(near_far) if near_far is not None else None
-        out = {"rgb": torch.empty(n, 3, device=dev), "depth": torch.empty(n, device=dev)}
+        out = {} if eval_only else {"rgb": torch.empty(n, 3, device=dev), "depth": torch.empty(n, device=dev)}
         if "acc" in want:
             out["acc"] = torch.empty(n, device=dev)
         if "weights" in want:
@@ -1478,7 +1514,7 @@ class RenderPass:
         p.u_sampled, p.wu_map = _ptr(out.get("u")), _ptr(out.get("wu"))
         _alive = self._coords(p, coords, n * S)      # noqa: F841 (kept until the launch is enqueued)
         p.rays_d, p.z, p.near_far, p.workspace = _ptr(rays_d), _ptr(z), _ptr(near_far), _ptr(self._ws)
-        p.rgb_map, p.depth_map, p.acc_map = _ptr(out["rgb"]), _ptr(out["depth"]), _ptr(out.get("acc"))
+        p.rgb_map, p.depth_map, p.acc_map = _ptr(out.get("rgb")), _ptr(out.get("depth")), _ptr(out.get("acc"))
         p.weights, p.var, p.raw, p.feats = _ptr(out.get("weights")), _ptr(out.get("var")), _ptr(out.get("raw")), _ptr(out.get("feats"))
         p.ev_mlp_start, p.ev_mlp_stop = events if events is not None else (None, None)
         p.train_workspace = None

@@ -2,9 +2,12 @@
 (ray_marcher -> render -> sample_pdf on mid-points with w[1:-1] -> sorted merge -> render).
 
 Library calls per batch (+ the source repack when asked), all on the caller's stream:
-  ray_gen_sample (rays + coarse depths) -> render_fused_fwd (coarse; its compositing launch also runs sample_pdf + merge) -> render_fused_fwd (fine).
+  ray_gen_sample (rays + coarse depths) -> render_fused_fwd (coarse; its compositing launch also runs sample_pdf + merge) -> render_fused_fwd (the
+  network on the n_fine NEW depths, evaluation only) -> composite_merged_fwd (compositing over the new rows and the coarse pass's kept rows, read
+  in merged order: no merged array).
   Five kernel launches per step on the gather-fused route (rays, MLP, composite + re-sample, MLP, composite); `fold_rays` moves the first into the
-  coarse MLP launch (four launches; measured slower, off by default).
+  coarse MLP launch (four launches; measured slower, off by default).  With reuse_coarse=False the fine pass is one render_fused_fwd over all
+  n_coarse + n_fine depths instead (what the reference computes; the renders are bit-identical): five launches as well.
 """
 import torch
 
@@ -63,6 +66,8 @@ class CoarseFineRenderer:
         # correctly rounded divisions and a square root per lane and tile, twice, are ~200 vector instructions in a kernel where none is free).  On the
         # tail route of small passes a block owns whole rays and makes them once, in its prologue: free.  None = that case only.
         self.fold_rays = None
+        # what the last render() did in the fine pass: "new_depths" (network on the n_fine new depths, coarse rows reused) or "all_depths", and why
+        self.fine_route, self.fine_route_reason = None, None
 
     def set_params(self, flat_params):
         self.wstream.copy_(self.pw.pack(flat_params))
@@ -77,19 +82,47 @@ class CoarseFineRenderer:
             return self.pass_small
         return self.pass_
 
-    def render(self, xs, ys, perturb=0.0, noise=None, u=None, events=None, repack=True, reuse_coarse=False):
+    def _reuse_by_default(self, n):
+        """(reuse?, reason) for reuse_coarse=None: the fine pass takes the coarse depths' rows from the coarse pass unless they would not be the
+        bits a full evaluation gives, or the library says the reuse does not pay at this size (ucnerf_reuse_coarse_pays)."""
+        nc, nf = self.n_coarse, self.n_fine
+        if self.pw.guarded or (self.pass_small is not None and self.pw_small.guarded):
+            # "fp16_guarded": a fine launch that saturates replays itself on bf16 terms while the kept coarse rows came from fp16 terms -- the
+            # merged rows would mix the two and not equal the all-depths replay
+            return False, "fp16_guarded operand mode"
+        if len({id(self._pass_for(n * k)) for k in (nc, nf, nc + nf)}) != 1:
+            # fused_min_rounds puts the passes on different kernels: their rows are not bit-identical to each other
+            return False, "fused_min_rounds: the passes run on different kernels"
+        fpass = self._pass_for(n * (nc + nf))
+        if (fpass.pw.cfg.precision == 3 and fpass.use_cl and not self.src.cl_bf16 and not self.max_blocks
+                and not L.lib().ucnerf_reuse_coarse_pays(n, nc, nf)):
+            # the pass over all depths composites inside its MLP launch (DESIGN.md 4.4): one launch; the reuse would put a compositing launch back
+            return False, "tail route: the all-depths pass is one launch"
+        return True, "default"
+
+    def render(self, xs, ys, perturb=0.0, noise=None, u=None, events=None, repack=True, reuse_coarse=None):
         """xs, ys: pixel coordinates [n] (device, float32).  events: optional [(start, stop), (start, stop)]
         Event pairs recorded around the coarse and the fine MLP launches.  repack: rebuild the channel-last source
         copies first (needed whenever volumes / images / features changed since the last call).
         reuse_coarse: the fine pass evaluates the network on the n_fine NEW depths only and takes the n_coarse coarse
         depths' outputs from the coarse pass (a sample's output depends on nothing but that sample, so the merged
         rows -- and everything composited from them -- are bit-identical to re-evaluating all n_coarse + n_fine, which is
-        what the reference and the default do): one third less network and gather work in the fine pass."""
+        what the reference does): one third less network and gather work in the fine pass.  None (default): the renderer
+        decides -- reuse, except where the rows would not be the full evaluation's bits or the all-depths pass is small enough to
+        composite inside its own MLP launch (_reuse_by_default); the returned
+        dict is that of reuse_coarse=False, name for name.  True / False force the choice; True also returns the working
+        buffers (coarse["raw"], the merge rank, "disp").  self.fine_route names what was done."""
         sc = self.scene
         if repack:
             self.pass_.repack_sources()
         # rays and their view-direction feature from one launch; both passes take the feature as an input
         n = int(xs.shape[0])
+        explicit = reuse_coarse is not None
+        if explicit:
+            reuse_coarse, why = bool(reuse_coarse), "forced"
+        else:
+            reuse_coarse, why = self._reuse_by_default(n)
+        self.fine_route, self.fine_route_reason = ("new_depths" if reuse_coarse else "all_depths"), why
         cpass = self._pass_for(n * self.n_coarse)
         # fold_rays (gather-fused kernel, up to six source views): the coarse launch generates rays, coarse depths and direction features itself
         # (ABI v4 gen_rays / gen_depths) -- no ray_gen_sample launch
@@ -111,16 +144,17 @@ class CoarseFineRenderer:
             hs = ops.sample_pdf(None, coarse["weights"], self.u_det if u is None else u, z_merge=z_c, want_inds=False,
                                 from_coarse=True, want_rank=reuse_coarse)
         if reuse_coarse:
-            new = self._pass_for(n * self.n_fine)(rays_d, hs["samples"], want=(), events=ev[1], keep=("raw",), dir_feat=angle)
-            raw = ops.merge_rows(new["raw"], coarse["raw"], hs["merge_rank"])      # cat(samples, z_coarse) order
-            out = ops.composite_fwd(raw, hs["z_sorted"], 0, self.white_bkgd)
+            new = self._pass_for(n * self.n_fine)(rays_d, hs["samples"], want=None, events=ev[1], dir_feat=angle)      # (evaluation only: no compositing of its own)
+            out = ops.composite_merged_fwd(new["raw"], coarse["raw"], hs["merge_rank"], hs["z_sorted"], self.white_bkgd)      # cat(samples, z_coarse) order
+            if not explicit:                                    # the working buffers stay inside: the names of the all-depths route
+                del out["disp"], coarse["raw"], hs["merge_rank"]
         else:
             out = self._pass_for(n * (self.n_coarse + self.n_fine))(rays_d, hs["z_sorted"], want=("acc", "weights", "var"), events=ev[1], dir_feat=angle)
         out.update(z_coarse=z_c, z_fine=hs["z_sorted"], z_samples=hs["samples"], coarse=coarse, rays_d=rays_d)
         return out
 
     # ------------------------------------------------------------------------------------------------ HIP graph
-    def capture(self, n_rays, perturb=0.0, repack=True, reuse_coarse=False):
+    def capture(self, n_rays, perturb=0.0, repack=True, reuse_coarse=None):
         """Captures one render of `n_rays` rays into a HIP graph (the launch-bound regime of small
         per-GPU batches).  Returns a callable g(xs, ys, noise=None) -> the same dict as render(); its tensors are owned
         by the graph and overwritten by the next replay.  Every launch of the step goes to the capturing stream and
