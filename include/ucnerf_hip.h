@@ -553,7 +553,7 @@ int ucnerf_sample_pdf(const ucnerf_sample_pdf_params* p, void* stream);
 /* a9 of the coarse pass + a8 in ONE launch -- network/renderer.py:109-140 followed by data/ray_utils.py:216-219, as the hierarchical renderer
  * chains them (data/ray_utils.py:199-224): the wave that composites a ray re-samples it from the weights it has just computed.  `c` is the
  * compositing call (live variant, no uncertainty inputs), `s` the re-sampling in its from_coarse form with n == c->n, n_merge == c->S,
- * n_bins == c->S - 1; s->weights is ignored (the composite's weights, also written to c->weights when that is non-NULL) and s->z_merge, when
+ * n_bins == c->S - 1 and 3 <= c->S <= 1024 (the limit of ucnerf_composite_fwd); s->weights is ignored (the composite's weights, also written to c->weights when that is non-NULL) and s->z_merge, when
  * given, must equal c->z.  Results are those of ucnerf_composite_fwd(c) followed by ucnerf_sample_pdf(s with weights = c->weights), bit for bit. */
 int ucnerf_composite_sample_pdf(const ucnerf_composite_params* c, const ucnerf_sample_pdf_params* s, void* stream);
 

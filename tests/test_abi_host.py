@@ -89,6 +89,8 @@ def test_argument_validation_reports_instead_of_launching(L):
     assert lib.ucnerf_composite_sample_pdf(C.addressof(c), C.addressof(s), None) == -1
     s.from_coarse, s.z_merge = 1, 32                                                                              # z_merge, when given, must be the pass's own depths
     assert lib.ucnerf_composite_sample_pdf(C.addressof(c), C.addressof(s), None) == -1 and b"z_merge" in lib.ucnerf_last_error()
+    c.S, s.n_bins, s.n_merge, s.z_merge = 1025, 1024, 1025, 0                                                    # 64 lanes x 16 samples end at 1024: sample 1024 would never be composited
+    assert lib.ucnerf_composite_sample_pdf(C.addressof(c), C.addressof(s), None) == -1 and b"S = 1025 outside 3..1024" in lib.ucnerf_last_error()
     r = L.RenderParams()
     r.n, r.S, r.cfg = 4, 64, L.MlpConfig(6, 0, 3)
     r.rays_o = r.rays_d = r.z = r.workspace = r.wstream = r.rgb_map = r.depth_map = 16

@@ -202,7 +202,7 @@ def test_frozen_network_with_differentiable_features_matches_oracle_autograd(sd_
 
 # ---------------------------------------------------------------------------------------------- the launches folded into the coarse pass
 @pytest.mark.parametrize("S,M,u_kind", [(64, 128, "linspace"), (64, 128, "random"), (90, 45, "random"), (3, 7, "random"), (129, 300, "linspace"),
-                                        (200, 128, "random"), (300, 1024, "linspace")])
+                                        (200, 128, "random"), (300, 1024, "linspace"), (257, 64, "random"), (513, 64, "linspace"), (1024, 64, "random")])
 def test_compositing_fused_with_the_resampling_equals_the_two_launches_bit_for_bit(S, M, u_kind, sd_v7):
     """ABI v4 `ucnerf_render_params.resample` / `ucnerf_composite_sample_pdf`: network/renderer.py:109-140 followed by data/ray_utils.py:216-219 in ONE
     launch.  Same weights (the lane split of the compositing kernel), hence the same cdf, the same searchsorted indices, the same depths."""

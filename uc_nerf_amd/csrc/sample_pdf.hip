@@ -79,7 +79,8 @@ extern "C" int ucnerf_composite_sample_pdf(const ucnerf_composite_params* c, con
     UCNERF_REQUIRE(c->variant == 0 && !c->u && !c->wu, "composite_sample_pdf: the live compositing variant without uncertainty inputs");
     UCNERF_REQUIRE(!c->var || c->S >= 2, "composite_sample_pdf: var needs S >= 2");
     UCNERF_REQUIRE(((uintptr_t)c->raw & 15) == 0, "composite_sample_pdf: raw must be 16-byte aligned");
-    UCNERF_REQUIRE(s->from_coarse && s->n == c->n && s->n_merge == c->S && s->n_bins == c->S - 1 && c->S >= 3 && c->S <= PDF_MAX_BINS + 1,
+    UCNERF_REQUIRE(c->S <= 1024, "composite_sample_pdf: S = %d outside 3..1024 (the compositing body's limit, as composite_fwd)", c->S);
+    UCNERF_REQUIRE(s->from_coarse && s->n == c->n && s->n_merge == c->S && s->n_bins == c->S - 1 && c->S >= 3,
                    "composite_sample_pdf: the re-sampling must be the from_coarse form over the composited pass (n %d / %d, n_merge %d, n_bins %d, S %d)",
                    s->n, c->n, s->n_merge, s->n_bins, c->S);
     UCNERF_REQUIRE(!s->z_merge || s->z_merge == c->z, "composite_sample_pdf: z_merge, when given, must be the composited pass's depths");
