@@ -684,6 +684,65 @@ typedef struct ucnerf_depth_hypotheses_params ucnerf_depth_hypotheses_params;
 int ucnerf_depth_hypotheses(const ucnerf_depth_hypotheses_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * e1   evaluation metrics on the device -- utils/evaluation.py:8-74 (compute_errors, depth_evaluation) and :76-101 (rgb_evaluation: PSNR and
+ *      SSIM; LPIPS is a network and not part of this library).  The rendered images and depth maps stay where the render pass left them;
+ *      one small vector per call is all a host has to read.
+ * ---------------------------------------------------------------------------------------------- */
+/* Workspace of ucnerf_depth_eval and of ucnerf_image_eval on n images of H x W pixels, in floats (the larger of the two: one allocation serves
+ * both): the digit histograms of the selection, the per-block partial sums and counts of the reductions.  < 0 on a bad argument. */
+int64_t ucnerf_eval_workspace_floats(int32_t n, int32_t H, int32_t W);
+
+/* depth_evaluation (utils/evaluation.py:29-74) without its host loop.  valid(i) = gt > min_depth && gt < max_depth && (mask == NULL || mask != 0);
+ *   ratio = median(gt over all valid pixels of all images) / median(pred over the same pixels): the EXACT float32 medians as numpy forms them
+ *           (odd count: the middle value; even count N: fl(fl(a + b) / 2) of ranks N/2 - 1 and N/2), found by an 8-bit radix selection on
+ *           order-preserving keys -- 4 histogram launches and 4 one-block pick launches, integer counts only (reproducible), nothing compacted;
+ *   per image and valid pixel, in float32 and in the reference's order: p = clamp(pred * ratio, min_depth, max_depth), t = max(gt / p, p / gt),
+ *           the counts of t < 1.25, < 1.5625, < 1.953125 and the sums of (gt - p)^2, (log gt - log p)^2, |gt - p| / gt, (gt - p)^2 / gt: per-block
+ *           partials, summed in a fixed order by a second launch (no float atomics: the same bits on every run).
+ * raw != 0 is compute_errors (:8-26) on its own: every pixel valid, p = pred as given, no medians (mask, min_depth, max_depth not read).
+ * out [4 + 12 n] 32-bit words:
+ *   out[0] ratio (float; NaN when no pixel is valid; 1 with raw)   out[1] int32: 1 when no pixel of any image is valid
+ *   out[2], out[3] the two medians (gt, pred)
+ *   per image i at out + 4 + 12 i: int32 valid count, count(a1), count(a2), count(a3); float abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3 (each mean =
+ *   sum / float(count), rmse = sqrt(mean); a_k = float(count_k) / float(count)); int32 flag: 1 when the image has no valid pixel (its seven
+ *   values are then NaN, and the reference leaves it out of the mean over images).
+ * n, H, W >= 1, n <= 65535 and n * H * W < 2^31; a NULL gt / pred / workspace / out, a workspace not 8-byte aligned and min_depth > max_depth are UCNERF_EINVAL.
+ * 10 launches + 1 memset (3 launches with raw), whatever the data; nothing is read back.  NaN depths are never valid; a NaN PREDICTION on a
+ * valid pixel sorts above +inf here, where numpy's median would answer NaN. */
+struct ucnerf_depth_eval_params {
+    int32_t n, H, W;
+    int32_t raw;               /* 1: compute_errors on gt / pred as they are */
+    float min_depth, max_depth;
+    const float* gt;           /* [n,H,W] */
+    const float* pred;         /* [n,H,W] */
+    const uint8_t* mask;       /* [n,H,W] or NULL */
+    float* workspace;          /* ucnerf_eval_workspace_floats(n, H, W) floats, 8-byte aligned */
+    float* out;                /* [4 + 12 n] words, see above */
+};
+typedef struct ucnerf_depth_eval_params ucnerf_depth_eval_params;
+int ucnerf_depth_eval(const ucnerf_depth_eval_params* p, void* stream);
+
+/* rgb_evaluation's per-image numbers (utils/evaluation.py:82-83, :89-96) for images gt, pred [n,3,H,W]:
+ *   mse  = float32 sum of (gt - pred)^2 over the image / float(3 H W)  (per-block partials, fixed order);   psnr = -10 log10(mse);
+ *   ssim = skimage.metrics.structural_similarity(data_range=1, channel_axis=2, everything else default): uniform 7 x 7 window per channel,
+ *          C1 = 1e-4, C2 = 9e-4, sample covariances v = 49/48 (uxx - ux ux), S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),
+ *          the mean of S over the windows that lie inside the image, then over the channels.  Window sums, S and its sums are carried in fp64
+ *          (products of two float32 values are exact there), the result is rounded to float32 once;
+ *   gt_max = the largest gt value of the image (what the reference's `assert gts.max() <= 1` needs).
+ * out [n,4] = (mse, psnr, ssim, gt_max).  1 <= n <= 65535, H >= 7, W >= 7 (skimage refuses a smaller image too; with no_ssim
+ * any H, W >= 1), 3 n H W < 2^31.  3 launches (2 with no_ssim). */
+struct ucnerf_image_eval_params {
+    int32_t n, H, W;
+    int32_t no_ssim;           /* 1: the image error alone (ssim = NaN); any H, W >= 1 */
+    const float* gt;           /* [n,3,H,W] */
+    const float* pred;         /* [n,3,H,W] */
+    float* workspace;          /* ucnerf_eval_workspace_floats(n, H, W) floats, 8-byte aligned */
+    float* out;                /* [n,4] */
+};
+typedef struct ucnerf_image_eval_params ucnerf_image_eval_params;
+int ucnerf_image_eval(const ucnerf_image_eval_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a10  one fused render pass -- network/renderer.py:215-255 (rendering) with the projection of
  *      utils/utils.py:716-724 in front: rays + depths -> world points -> stage coordinates -> features ->
  *      PE + MLP -> composite.  Source views = pose entries 1..V of the reference's pose_ref

@@ -68,7 +68,7 @@ def set_backward_mode(mode):
 
 def install_dropin(precision=None, training_precision=None, split_operand=None):
     """Registers this package's mirrors under the reference's module names (`network.renderer`,
-    `network.models`, `network.mvs_models`, `utils.utils`, `utils.run_nerf_helpers`, `data.ray_utils`) so that the reference's
+    `network.models`, `network.mvs_models`, `utils.utils`, `utils.run_nerf_helpers`, `utils.evaluation`, `data.ray_utils`) so that the reference's
     train.py imports resolve here unchanged.  See INTEGRATION.md.
     precision: MLP arithmetic of `rendering()` under torch.no_grad() (None keeps the default, "bf16x3_fused"; "f32" = exact fp32 MFMA);
     training_precision: of the training forward (None keeps "f32");
@@ -88,7 +88,7 @@ def install_dropin(precision=None, training_precision=None, split_operand=None):
             m = types.ModuleType(pkg)
             m.__path__ = []
             sys.modules[pkg] = m
-    for name in ("network.renderer", "network.models", "network.mvs_models", "utils.utils", "utils.run_nerf_helpers", "data.ray_utils"):
+    for name in ("network.renderer", "network.models", "network.mvs_models", "utils.utils", "utils.run_nerf_helpers", "utils.evaluation", "data.ray_utils"):
         mod = importlib.import_module("uc_nerf_amd." + name)
         sys.modules[name] = mod
         setattr(sys.modules[name.split(".")[0]], name.split(".")[1], mod)

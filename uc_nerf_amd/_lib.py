@@ -154,6 +154,15 @@ class BuildRaysTrainParams(C.Structure):
                 ("ndc", vp)]
 
 
+class DepthEvalParams(C.Structure):
+    _fields_ = [("n", i32), ("H", i32), ("W", i32), ("raw", i32), ("min_depth", f32), ("max_depth", f32), ("gt", vp), ("pred", vp), ("mask", vp),
+                ("workspace", vp), ("out", vp)]
+
+
+class ImageEvalParams(C.Structure):
+    _fields_ = [("n", i32), ("H", i32), ("W", i32), ("no_ssim", i32), ("gt", vp), ("pred", vp), ("workspace", vp), ("out", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -190,7 +199,8 @@ STRUCTS = {
 # structs added to ABI v6 after its struct table was fixed (STRUCTS above is that table, kept as it was: additive entry points move nothing in it);
 # checked against the library's sizeof() at load time like the others
 ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams,
-                 "ucnerf_composite_merged_params": CompositeMergedParams}
+                 "ucnerf_composite_merged_params": CompositeMergedParams, "ucnerf_depth_eval_params": DepthEvalParams,
+                 "ucnerf_image_eval_params": ImageEvalParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -254,6 +264,10 @@ SYMBOLS = {
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress_bwd": (C.c_int, [_P, _P]),
     "ucnerf_depth_hypotheses": (C.c_int, [_P, _P]),
+    # the evaluation metrics (additive to ABI v6)
+    "ucnerf_eval_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ucnerf_depth_eval": (C.c_int, [_P, _P]),
+    "ucnerf_image_eval": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

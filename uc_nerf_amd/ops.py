@@ -1387,6 +1387,59 @@ def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=
     return out
 
 
+# ------------------------------------------------------------------------------------------------ e1
+def _eval_workspace(n, H, W, dev):
+    floats = L.lib().ucnerf_eval_workspace_floats(n, H, W)
+    if floats < 0:
+        raise RuntimeError("uc_nerf_amd: eval workspace: %s" % L.lib().ucnerf_last_error().decode())
+    return torch.empty(floats, device=dev)
+
+
+def depth_eval(gt, pred, mask=None, min_depth=1e-4, max_depth=100., raw=False):
+    """Median-scaled depth errors of utils/evaluation.py:29-74 on the device.  gt, pred [n,H,W] float32, mask [n,H,W] uint8 or None (at the ground
+    truth's resolution).  Returns device tensors, nothing is read back and nothing synchronises:
+      ratio [1] (NaN when no pixel is valid), medians [2] (gt, pred), empty [1] int32 (1: no valid pixel in any image),
+      counts [n,4] int32 (valid, a1, a2, a3), errors [n,7] float32 (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3),
+      flags [n] int32 (1: the image has no valid pixel -- the reference leaves it out of its mean), packed [4 + 12 n]: all of it in one tensor.
+    raw=True: compute_errors (:8-26) on the values as given -- every pixel valid, no scaling, no clamping."""
+    gt, pred = _f32(gt, "gt"), _f32(pred, "pred")
+    if gt.dim() != 3 or pred.shape != gt.shape or pred.device != gt.device:
+        raise RuntimeError("uc_nerf_amd.depth_eval: gt and pred must be [n,H,W] on one device, got %s and %s" % (tuple(gt.shape), tuple(pred.shape)))
+    if mask is not None:
+        _dev(mask)
+        if mask.dtype != torch.uint8 or mask.shape != gt.shape or mask.device != gt.device:
+            raise RuntimeError("uc_nerf_amd.depth_eval: mask must be uint8 of gt's shape on gt's device, got %s %s" % (mask.dtype, tuple(mask.shape)))
+        mask = mask.contiguous()
+    n, H, W = gt.shape
+    dev = gt.device
+    p = L.DepthEvalParams()
+    p.n, p.H, p.W, p.raw, p.min_depth, p.max_depth = n, H, W, int(raw), float(min_depth), float(max_depth)
+    ws = _eval_workspace(n, H, W, dev)
+    out = torch.empty(4 + 12 * n, device=dev)
+    p.gt, p.pred, p.mask, p.workspace, p.out = _ptr(gt), _ptr(pred), _ptr(mask), _ptr(ws), _ptr(out)
+    _launch("ucnerf_depth_eval", p, dev)
+    words, rows = out.view(torch.int32), out[4:].view(n, 12)
+    return dict(ratio=out[0:1], empty=words[1:2], medians=out[2:4], counts=rows[:, 0:4].view(torch.int32), errors=rows[:, 4:11],
+                flags=rows[:, 11].view(torch.int32), packed=out)
+
+
+def image_eval(gt, pred, ssim=True):
+    """Per-image mse, psnr and ssim of utils/evaluation.py:82-83, :89-96 on the device.  gt, pred [n,3,H,W] float32, H, W >= 7 (ssim=False: the image error alone, any size, ssim = NaN).  Returns device
+    tensors (no read-back, no synchronisation): mse [n], psnr [n], ssim [n], gt_max [n], packed [n,4]."""
+    gt, pred = _f32(gt, "gt"), _f32(pred, "pred")
+    if gt.dim() != 4 or gt.shape[1] != 3 or pred.shape != gt.shape or pred.device != gt.device:
+        raise RuntimeError("uc_nerf_amd.image_eval: gt and pred must be [n,3,H,W] on one device, got %s and %s" % (tuple(gt.shape), tuple(pred.shape)))
+    n, _, H, W = gt.shape
+    dev = gt.device
+    p = L.ImageEvalParams()
+    p.n, p.H, p.W, p.no_ssim = n, H, W, int(not ssim)
+    ws = _eval_workspace(n, H, W, dev)
+    out = torch.empty(n, 4, device=dev)
+    p.gt, p.pred, p.workspace, p.out = _ptr(gt), _ptr(pred), _ptr(ws), _ptr(out)
+    _launch("ucnerf_image_eval", p, dev)
+    return dict(mse=out[:, 0], psnr=out[:, 1], ssim=out[:, 2], gt_max=out[:, 3], packed=out)
+
+
 # ------------------------------------------------------------------------------------------------ a10
 class RenderPass:
     """Pre-bound arguments of ucnerf_render_fused_fwd for one scene; call it with (rays_d, z).
