@@ -599,6 +599,34 @@ struct ucnerf_composite_merged_params {
 typedef struct ucnerf_composite_merged_params ucnerf_composite_merged_params;
 int ucnerf_composite_merged_fwd(const ucnerf_composite_merged_params* p, void* stream);
 
+/* Backward of ucnerf_composite_merged_fwd (added to ABI v6; nothing above moved): the gradients of the rows of a sorted merge, read and written
+ * where they are.  g_raw_a / g_raw_b are, bit for bit, what three steps in sequence give -- ucnerf_merge_rows of raw_a / raw_b into [n,na+nb,4],
+ * ucnerf_composite_bwd (live variant) on that array and `z`, and taking row rank[j] of its g_raw for row j of cat(g_raw_a, g_raw_b) -- from ONE
+ * launch, with neither the merged rows nor their gradients in memory.  The wave that owns a ray inverts the ray's rank row in LDS as the forward
+ * does, loads merged position i from row inv[i] of raw_a or raw_b and stores its gradient to the same row of g_raw_a or g_raw_b; lane split
+ * (ceil((na+nb)/64) -> 1, 2, 3, 4, 8, 16 samples per lane), scans and arithmetic are those of ucnerf_composite_bwd.  rank is a permutation, so
+ * every gradient row is written exactly once: no atomics, no zero fill, and a second call into the same buffers gives the same bits.
+ * The upstream gradients are in merged order (the order of the forward's outputs); the results are in the order of raw_a / raw_b.
+ * 1 <= na + nb <= 1024, na >= 0, nb >= 0; raw_a / raw_b / g_raw_a / g_raw_b 16-byte aligned (a side may be NULL when its row count is 0).  As
+ * in the forward `rank` is NOT checked: other contents than a permutation give undefined values, never an access outside the arrays named here.
+ * (Declared with a struct tag: mirrored in _lib.ADDED_STRUCTS.) */
+struct ucnerf_composite_merged_bwd_params {
+    int32_t n, na, nb;         /* rays; rows per ray in raw_a / raw_b */
+    int32_t white_bkgd;
+    const float* raw_a;        /* [n,na,4] the forward's inputs ... */
+    const float* raw_b;        /* [n,nb,4] */
+    const int32_t* rank;       /* [n,na+nb] */
+    const float* z;            /* [n,na+nb] */
+    const float* g_rgb;        /* [n,3] or NULL */
+    const float* g_depth;      /* [n] or NULL */
+    const float* g_acc;        /* [n] or NULL */
+    const float* g_weights;    /* [n,na+nb] or NULL, in merged order */
+    float* g_raw_a;            /* [n,na,4] out, in the order of raw_a */
+    float* g_raw_b;            /* [n,nb,4] out, in the order of raw_b */
+};
+typedef struct ucnerf_composite_merged_bwd_params ucnerf_composite_merged_bwd_params;
+int ucnerf_composite_merged_bwd(const ucnerf_composite_merged_bwd_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * f2   the step in front of the path: cost-volume assembly and depth regression of one cascade stage.
  *      ucnerf_cost_volume replaces the loop of network/mvs_models.py:609-626: homo_warp (utils/utils.py:1105-1172,

@@ -122,6 +122,11 @@ class CompositeMergedParams(C.Structure):
                 ("depth_map", vp), ("acc_map", vp), ("disp_map", vp), ("weights", vp), ("var", vp), ("u", vp), ("wu", vp)]
 
 
+class CompositeMergedBwdParams(C.Structure):
+    _fields_ = [("n", i32), ("na", i32), ("nb", i32), ("white_bkgd", i32), ("raw_a", vp), ("raw_b", vp), ("rank", vp), ("z", vp), ("g_rgb", vp),
+                ("g_depth", vp), ("g_acc", vp), ("g_weights", vp), ("g_raw_a", vp), ("g_raw_b", vp)]
+
+
 class CostVolumeParams(C.Structure):
     _fields_ = [("V", i32), ("C", i32), ("H", i32), ("W", i32), ("D", i32), ("pad", i32), ("feats", vp), ("proj", vp),
                 ("depth_values", vp), ("variance", vp), ("count", vp)]
@@ -200,7 +205,7 @@ STRUCTS = {
 # checked against the library's sizeof() at load time like the others
 ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams,
                  "ucnerf_composite_merged_params": CompositeMergedParams, "ucnerf_depth_eval_params": DepthEvalParams,
-                 "ucnerf_image_eval_params": ImageEvalParams}
+                 "ucnerf_image_eval_params": ImageEvalParams, "ucnerf_composite_merged_bwd_params": CompositeMergedBwdParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -259,6 +264,7 @@ SYMBOLS = {
     "ucnerf_composite_sample_pdf": (C.c_int, [_P, _P, _P]),
     "ucnerf_merge_rows": (C.c_int, [_P, _P]),
     "ucnerf_composite_merged_fwd": (C.c_int, [_P, _P]),
+    "ucnerf_composite_merged_bwd": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),

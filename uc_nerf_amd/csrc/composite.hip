@@ -45,60 +45,45 @@ __global__ void __launch_bounds__(256) composite_merged_fwd_kernel(ucnerf_compos
     composite_ray<E, 0>(p, ray, lane, nullptr, rows);
 }
 
-// Backward of the live variant.  With gw_i = dL/dw_i:
-//   dL/dalpha_i = gw_i T_i - (sum_{k>i} gw_k w_k) / f_i,   dL/dsigma_i = dL/dalpha_i * exp(-sigma_i),
-//   dL/drgb_i = w_i * g_rgb.
+// Backward of the live variant (composite_bwd_ray of composite_device.h) over the dense array fwd.raw, gradients into g_raw.
 template <int E>
 __global__ void __launch_bounds__(256) composite_bwd_kernel(ucnerf_composite_bwd_params bp) {
     const ucnerf_composite_params& p = bp.fwd;
     const int lane = threadIdx.x & 63;
     const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= p.n) return;
-    float gr = 0.f, gg = 0.f, gb = 0.f, gd = 0.f, ga = 0.f;
-    if (bp.g_rgb) { gr = bp.g_rgb[3 * (size_t)ray]; gg = bp.g_rgb[3 * (size_t)ray + 1]; gb = bp.g_rgb[3 * (size_t)ray + 2]; }
-    if (bp.g_depth) gd = bp.g_depth[ray];
-    if (bp.g_acc) ga = bp.g_acc[ray];
-    if (p.white_bkgd) ga -= gr + gg + gb;       // rgb_map += 1 - acc
-    Sample sm[E];
-    float T[E], em[E];
-    float prod = 1.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = lane * E + e;
-        sm[e] = load_sample<0>(p, ray, i, 0.f);
-        em[e] = sm[e].ex;                       // exp(-sigma) = d(alpha)/d(sigma)
-        T[e] = prod;
-        prod *= sm[e].f;
-    }
-    const float pre = wave_excl_prod(prod, lane);
-    float gw[E], gww[E];
-    float local = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = lane * E + e;
-        T[e] *= pre;
-        gw[e] = 0.f; gww[e] = 0.f;
-        if (i < p.S) {
-            gw[e] = gr * sm[e].r + gg * sm[e].g + gb * sm[e].b + gd * p.z[(size_t)ray * p.S + i] + ga;
-            if (bp.g_weights) gw[e] += bp.g_weights[(size_t)ray * p.S + i];
-            gww[e] = gw[e] * sm[e].alpha * T[e];
-            local += gww[e];
+    const CompositeUpstream up{bp.g_rgb, bp.g_depth, bp.g_acc, bp.g_weights};
+    composite_bwd_ray<E>(p, up, ray, lane, DenseRows(), DenseGradRows{reinterpret_cast<float4*>(bp.g_raw)});
+}
+
+// The same backward over the rows of a sorted merge, read and written where they are (ucnerf_composite_merged_bwd): the wave inverts its ray's rank
+// row through LDS as composite_merged_fwd_kernel does, loads merged position i from row inv[i] of a or b and stores its gradient to row inv[i] of
+// g_raw_a or g_raw_b.  rank is a permutation: every gradient row is written exactly once -- no atomics, no zero fill.
+template <int E>
+__global__ void __launch_bounds__(256) composite_merged_bwd_kernel(ucnerf_composite_merged_bwd_params m) {
+    extern __shared__ int inv_all[];            // [4 waves][S]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ray = blockIdx.x * 4 + wave;
+    const int S = m.na + m.nb;
+    int* inv = inv_all + wave * S;
+    if (ray < m.n) {
+        const int* rank = m.rank + (size_t)ray * S;
+        for (int j = lane; j < S; j += 64) {
+            const unsigned r = (unsigned)rank[j];
+            if (r < (unsigned)S) inv[r] = j;      // (a rank outside the row is dropped: nothing outside this wave's S ints is written)
         }
     }
-    float suffix = wave_excl_suffix_sum(local, lane);   // contributions of higher lanes
-#pragma unroll
-    for (int e = E - 1; e >= 0; --e) {
-        const int i = lane * E + e;
-        if (i < p.S) {
-            const float w = sm[e].alpha * T[e];
-            const float galpha = gw[e] * T[e] - suffix / sm[e].f;
-            float4 o;
-            o.x = w * gr; o.y = w * gg; o.z = w * gb;
-            o.w = galpha * em[e];
-            reinterpret_cast<float4*>(bp.g_raw)[(size_t)ray * p.S + i] = o;
-        }
-        suffix += gww[e];
-    }
+    __syncthreads();
+    if (ray >= m.n) return;
+    ucnerf_composite_params p;
+    p.n = m.n; p.S = S; p.variant = 0; p.white_bkgd = m.white_bkgd;
+    p.raw = nullptr; p.z = m.z; p.rays_d = nullptr; p.noise = nullptr;
+    p.rgb_map = nullptr; p.depth_map = nullptr; p.acc_map = nullptr; p.disp_map = nullptr;
+    p.weights = nullptr; p.var = nullptr; p.u = nullptr; p.wu = nullptr;
+    const CompositeUpstream up{m.g_rgb, m.g_depth, m.g_acc, m.g_weights};
+    const MergedRows rows{reinterpret_cast<const float4*>(m.raw_a), reinterpret_cast<const float4*>(m.raw_b), m.na, m.nb, inv};
+    const MergedGradRows sink{reinterpret_cast<float4*>(m.g_raw_a), reinterpret_cast<float4*>(m.g_raw_b), m.na, m.nb, inv};
+    composite_bwd_ray<E>(p, up, ray, lane, rows, sink);
 }
 
 template <int E>
@@ -178,6 +163,30 @@ int ucnerf_composite_bwd(const ucnerf_composite_bwd_params* bp, void* stream) {
     else if (E <= 8) hipLaunchKernelGGL(composite_bwd_kernel<8>, grid, block, 0, st, *bp);
     else hipLaunchKernelGGL(composite_bwd_kernel<16>, grid, block, 0, st, *bp);
     return check_launch("composite_bwd");
+}
+
+int ucnerf_composite_merged_bwd(const ucnerf_composite_merged_bwd_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "composite_merged_bwd: null params");
+    UCNERF_COUNT(p->n);
+    UCNERF_REQUIRE(p->na >= 0 && p->nb >= 0, "composite_merged_bwd: negative row count (na = %d, nb = %d)", p->na, p->nb);
+    const long long S = (long long)p->na + p->nb;
+    UCNERF_REQUIRE(S >= 1 && S <= 1024, "composite_merged_bwd: na + nb = %lld outside 1..1024", S);
+    UCNERF_REQUIRE(((p->raw_a && p->g_raw_a) || p->na == 0) && ((p->raw_b && p->g_raw_b) || p->nb == 0) && p->rank && p->z,
+                   "composite_merged_bwd: null pointer");
+    UCNERF_REQUIRE((((uintptr_t)p->raw_a | (uintptr_t)p->raw_b | (uintptr_t)p->g_raw_a | (uintptr_t)p->g_raw_b) & 15) == 0,
+                   "composite_merged_bwd: raw_a, raw_b, g_raw_a and g_raw_b must be 16-byte aligned");
+    UCNERF_REQUIRE(((uintptr_t)p->rank & 3) == 0, "composite_merged_bwd: rank must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(cdiv(p->n, 4)), block(256);
+    const size_t lds = 4 * (size_t)S * sizeof(int);      // one inverse per wave: at most 16 KB
+    const int E = cdiv(S, 64);                           // the lane split of ucnerf_composite_bwd at this S: same gradients, bit for bit
+    if (E <= 1) hipLaunchKernelGGL(composite_merged_bwd_kernel<1>, grid, block, lds, st, *p);
+    else if (E <= 2) hipLaunchKernelGGL(composite_merged_bwd_kernel<2>, grid, block, lds, st, *p);
+    else if (E <= 3) hipLaunchKernelGGL(composite_merged_bwd_kernel<3>, grid, block, lds, st, *p);
+    else if (E <= 4) hipLaunchKernelGGL(composite_merged_bwd_kernel<4>, grid, block, lds, st, *p);
+    else if (E <= 8) hipLaunchKernelGGL(composite_merged_bwd_kernel<8>, grid, block, lds, st, *p);
+    else hipLaunchKernelGGL(composite_merged_bwd_kernel<16>, grid, block, lds, st, *p);
+    return check_launch("composite_merged_bwd");
 }
 
 }  // extern "C"

@@ -150,6 +150,90 @@ __device__ __forceinline__ void composite_ray(const ucnerf_composite_params& p, 
     composite_ray<E, VARIANT>(p, ray, lane, w_keep, DenseRows());
 }
 
+// where a ray's gradient rows [.,4] go: Sink()(p, ray, i, o) stores the gradient of row i (i < p.S) of ray `ray`.  DenseGradRows: g_raw [n,S,4]
+struct DenseGradRows {
+    float4* g;
+    __device__ __forceinline__ void operator()(const ucnerf_composite_params& p, int ray, int i, const float4& o) const {
+        g[(size_t)ray * p.S + i] = o;
+    }
+};
+
+// The counterpart of MergedRows (ucnerf_composite_merged_bwd): the gradient of merged position i goes to row inv[i] of cat(a[ray], b[ray]), the
+// row MergedRows read it from -- same inverse, same clamp (memory-safe for any rank contents; a permutation writes every row exactly once).
+struct MergedGradRows {
+    float4* a;              // [n,na]
+    float4* b;              // [n,nb]
+    int na, nb;
+    const int* inv;         // [na+nb]
+    __device__ __forceinline__ void operator()(const ucnerf_composite_params& p, int ray, int i, const float4& o) const {
+        const int j = min((unsigned)inv[i], (unsigned)(na + nb - 1));
+        if (j < na) a[(size_t)ray * na + j] = o;
+        else b[(size_t)ray * nb + (j - na)] = o;
+    }
+};
+
+// upstream gradients of a ray's outputs; each may be NULL (= zero)
+struct CompositeUpstream {
+    const float* g_rgb;        // [n,3]
+    const float* g_depth;      // [n]
+    const float* g_acc;        // [n]
+    const float* g_weights;    // [n,S]
+};
+
+// Backward of the live variant of one ray by one 64-lane wave, lane split as in composite_ray.  With gw_i = dL/dw_i:
+//   dL/dalpha_i = gw_i T_i - (sum_{k>i} gw_k w_k) / f_i,   dL/dsigma_i = dL/dalpha_i * exp(-sigma_i),
+//   dL/drgb_i = w_i * g_rgb.
+// `rows`: where the raw rows are read from; `sink`: where their gradients go.  Everything between is the one body every compositing backward runs.
+template <int E, class Rows, class Sink>
+__device__ __forceinline__ void composite_bwd_ray(const ucnerf_composite_params& p, const CompositeUpstream& up, int ray, int lane, const Rows& rows,
+                                                  const Sink& sink) {
+    float gr = 0.f, gg = 0.f, gb = 0.f, gd = 0.f, ga = 0.f;
+    if (up.g_rgb) { gr = up.g_rgb[3 * (size_t)ray]; gg = up.g_rgb[3 * (size_t)ray + 1]; gb = up.g_rgb[3 * (size_t)ray + 2]; }
+    if (up.g_depth) gd = up.g_depth[ray];
+    if (up.g_acc) ga = up.g_acc[ray];
+    if (p.white_bkgd) ga -= gr + gg + gb;       // rgb_map += 1 - acc
+    Sample sm[E];
+    float T[E], em[E];
+    float prod = 1.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = lane * E + e;
+        sm[e] = load_sample<0>(p, ray, i, 0.f, rows);
+        em[e] = sm[e].ex;                       // exp(-sigma) = d(alpha)/d(sigma)
+        T[e] = prod;
+        prod *= sm[e].f;
+    }
+    const float pre = wave_excl_prod(prod, lane);
+    float gw[E], gww[E];
+    float local = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = lane * E + e;
+        T[e] *= pre;
+        gw[e] = 0.f; gww[e] = 0.f;
+        if (i < p.S) {
+            gw[e] = gr * sm[e].r + gg * sm[e].g + gb * sm[e].b + gd * p.z[(size_t)ray * p.S + i] + ga;
+            if (up.g_weights) gw[e] += up.g_weights[(size_t)ray * p.S + i];
+            gww[e] = gw[e] * sm[e].alpha * T[e];
+            local += gww[e];
+        }
+    }
+    float suffix = wave_excl_suffix_sum(local, lane);   // contributions of higher lanes
+#pragma unroll
+    for (int e = E - 1; e >= 0; --e) {
+        const int i = lane * E + e;
+        if (i < p.S) {
+            const float w = sm[e].alpha * T[e];
+            const float galpha = gw[e] * T[e] - suffix / sm[e].f;
+            float4 o;
+            o.x = w * gr; o.y = w * gg; o.z = w * gb;
+            o.w = galpha * em[e];
+            sink(p, ray, i, o);
+        }
+        suffix += gww[e];
+    }
+}
+
 // E (samples per lane) the launchers instantiate for S samples per ray: the association order of the transmittance products depends on it,
 // so every kernel that composites a ray of S samples must pick the same one
 __host__ __device__ inline int composite_lane_samples(int S) {

@@ -1247,6 +1247,63 @@ def composite_merged_fwd(raw_a, raw_b, rank, z, white_bkgd=False, want_var=True,
     return out
 
 
+def composite_merged_bwd(raw_a, raw_b, rank, z, g_rgb=None, g_depth=None, g_acc=None, g_weights=None, white_bkgd=False, out=None):
+    """(g_raw_a [n,na,4], g_raw_b [n,nb,4]): composite_bwd(merge_rows(raw_a, raw_b, rank), z, ...) taken back through rank, from one launch, bit for
+    bit, with no merged array.  The upstream gradients (each optional) are in merged order.  out: (g_raw_a, g_raw_b) buffers to write into --
+    every row is written, whatever they held."""
+    raw_a, raw_b, z = _f32(raw_a, "raw_a"), _f32(raw_b, "raw_b"), _f32(z, "z")
+    n, S = z.shape
+    na, nb = raw_a.shape[1], raw_b.shape[1]
+    if (rank.dtype != torch.int32 or tuple(rank.shape) != (n, S) or tuple(raw_a.shape) != (n, na, 4) or tuple(raw_b.shape) != (n, nb, 4)
+            or na + nb != S or rank.device != z.device):
+        raise RuntimeError("uc_nerf_amd.composite_merged_bwd: shape / dtype mismatch")
+    rank = rank.contiguous()
+    gs = [_f32(g) if g is not None else None for g in (g_rgb, g_depth, g_acc, g_weights)]
+    for g, numel, name in zip(gs, (3 * n, n, n, n * S), ("g_rgb", "g_depth", "g_acc", "g_weights")):
+        if g is not None and g.numel() != numel:
+            raise RuntimeError("uc_nerf_amd.composite_merged_bwd: %s has %d elements, expected %d" % (name, g.numel(), numel))
+    if out is None:
+        out = (torch.empty_like(raw_a), torch.empty_like(raw_b))
+    g_a, g_b = out
+    if (tuple(g_a.shape) != (n, na, 4) or tuple(g_b.shape) != (n, nb, 4) or g_a.dtype != torch.float32 or g_b.dtype != torch.float32
+            or not g_a.is_contiguous() or not g_b.is_contiguous() or g_a.device != z.device or g_b.device != z.device):
+        raise RuntimeError("uc_nerf_amd.composite_merged_bwd: out must be contiguous float32 (g_raw_a [n,na,4], g_raw_b [n,nb,4]) on the device")
+    p = L.CompositeMergedBwdParams()
+    p.n, p.na, p.nb, p.white_bkgd = n, na, nb, int(white_bkgd)
+    p.raw_a, p.raw_b, p.rank, p.z = _ptr(raw_a) if na else None, _ptr(raw_b) if nb else None, _ptr(rank), _ptr(z)
+    p.g_rgb, p.g_depth, p.g_acc, p.g_weights = (_ptr(g) for g in gs)
+    p.g_raw_a, p.g_raw_b = _ptr(g_a) if na else None, _ptr(g_b) if nb else None
+    _launch("ucnerf_composite_merged_bwd", p, z.device)
+    return g_a, g_b
+
+
+class _CompositeMerged(torch.autograd.Function):
+    """raw2outputs (live variant) over the rows of a sorted merge: differentiable w.r.t. raw_a and raw_b through rgb_map, depth_map, acc_map and
+    weights.  Upstream gradients autograd leaves out (None) reach the kernel as NULL pointers."""
+
+    @staticmethod
+    def forward(ctx, raw_a, raw_b, rank, z, white_bkgd):
+        out = composite_merged_fwd(raw_a, raw_b, rank, z, white_bkgd)
+        ctx.save_for_backward(raw_a, raw_b, rank, z)
+        ctx.white_bkgd = white_bkgd
+        ctx.set_materialize_grads(False)
+        var = out.get("var", torch.zeros_like(out["acc"]))
+        ctx.mark_non_differentiable(out["disp"], var)
+        return out["rgb"], out["depth"], out["acc"], out["weights"], out["disp"], var
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_acc, g_weights, _g_disp, _g_var):
+        raw_a, raw_b, rank, z = ctx.saved_tensors
+        g_a, g_b = composite_merged_bwd(raw_a, raw_b, rank, z, g_rgb, g_depth, g_acc, g_weights, ctx.white_bkgd)
+        return g_a, g_b, None, None, None
+
+
+def composite_merged(raw_a, raw_b, rank, z, white_bkgd=False):
+    """(rgb, depth, acc, weights, disp, var) of composite(merge_rows(raw_a, raw_b, rank), z, white_bkgd) with no merged array, forward
+    (composite_merged_fwd) and backward (composite_merged_bwd): gradients for raw_a and raw_b, each in its own order."""
+    return _CompositeMerged.apply(raw_a, raw_b, rank, z, bool(white_bkgd))
+
+
 # ------------------------------------------------------------------------------------------------ f2
 def _cost_volume_params(feats, proj, depth_values, pad):
     V, Cc, H, W = feats.shape

@@ -8,6 +8,8 @@ Library calls per batch (+ the source repack when asked), all on the caller's st
   Five kernel launches per step on the gather-fused route (rays, MLP, composite + re-sample, MLP, composite); `fold_rays` moves the first into the
   coarse MLP launch (four launches; measured slower, off by default).  With reuse_coarse=False the fine pass is one render_fused_fwd over all
   n_coarse + n_fine depths instead (what the reference computes; the renders are bit-identical): five launches as well.
+
+Training: render_train() is the same composition from the differentiable ops (feat_gather, mlp, composite, composite_merged), exact f32.
 """
 import torch
 
@@ -152,6 +154,54 @@ class CoarseFineRenderer:
             out = self._pass_for(n * (self.n_coarse + self.n_fine))(rays_d, hs["z_sorted"], want=("acc", "weights", "var"), events=ev[1], dir_feat=angle)
         out.update(z_coarse=z_c, z_fine=hs["z_sorted"], z_samples=hs["samples"], coarse=coarse, rays_d=rays_d)
         return out
+
+    # ------------------------------------------------------------------------------------------------ training
+    def _train_coords(self, rays_d, z):
+        """(pts [n,S,3], dict stage1, stage2, stage3, ndc) at the depths z: world points o + z d in the order of the render pass's own kernel, and
+        their stage coordinates as RenderPass derives them (scene near / far for every stage).  No gradient: positions are not differentiable here."""
+        if not hasattr(self, "_K_ref_host"):
+            self._K_ref_host = self.scene["intrinsics"][0].detach().cpu()
+        pts = (self.pass_.rays_o.view(1, 1, 3) + z.unsqueeze(-1) * rays_d.unsqueeze(1)).contiguous()
+        nf = dict.fromkeys(("near_1", "near_2", "near_3"), self.near_host)
+        nf.update(dict.fromkeys(("far_1", "far_2", "far_3"), self.far_host), near=self.near_host, far=self.far_host)
+        return pts, ops.ndc_project(pts, self.w2c_dir_host, self._K_ref_host, [self.src.W - 1, self.src.H - 1], nf)
+
+    def _eval_train(self, flat_params, wstream, rays_d, angle, z):
+        """raw [n,S,4] at the depths z with autograd history: ops.feat_gather on the scene's own tensors, ops.mlp on `flat_params`."""
+        sc = self.scene
+        n, S = z.shape
+        if not hasattr(self, "_w2cs_src"):
+            self._w2cs_src, self._intr_src = sc["w2cs"][1:].detach().contiguous(), sc["intrinsics"][1:].detach().contiguous()
+        pts, ndc = self._train_coords(rays_d, z)
+        feats = ops.feat_gather(sc["vols"], sc["confidence"], sc["img_feat"], sc["imgs"], self._w2cs_src, self._intr_src, pts,
+                                ndc["stage1"], ndc["stage2"], ndc["stage3"])
+        return ops.mlp(flat_params, feats, ndc["ndc"], angle, self.pw, S, wstream).view(n, S, 4)
+
+    def render_train(self, xs, ys, flat_params, perturb=0.0, noise=None, u=None):
+        """render(reuse_coarse=True) with autograd history: the same dict, name for name (rgb, depth, acc, disp, weights, var, coarse{rgb, depth,
+        weights, raw, samples, z_sorted, merge_rank}, z_coarse, z_fine, z_samples, rays_d; disp and var carry no gradient), differentiable back to `flat_params` and to whichever of the scene's volumes, image features and confidence
+        have requires_grad.  xs, ys, perturb, noise, u: as in render().
+        Route: sampler -> gather + MLP at the coarse depths (ops.feat_gather, ops.mlp) -> ops.composite; its weights, detached, draw the new
+        depths (ops.sample_pdf: no gradient, as in the reference) -> gather + MLP at the NEW depths only -> ops.composite_merged over the new rows
+        and the coarse rows.  The coarse rows receive gradient twice -- from the coarse compositing and, as raw_b, from the fine one -- and
+        autograd sums the two.  The network runs on a stream packed from `flat_params` here (the renderer's own stream is not touched).
+        Exact-f32 precision only."""
+        if self.pw.guarded:
+            raise RuntimeError("uc_nerf_amd.CoarseFineRenderer.render_train: the 'fp16_guarded' operand mode is an inference mode -- a launch that "
+                               "saturates replays itself on other terms, which no backward follows; train with precision='f32'")
+        if self.precision != "f32":
+            raise RuntimeError("uc_nerf_amd.CoarseFineRenderer.render_train: precision %r has no training forward in the ops layer (ops.mlp's "
+                               "backward re-runs the network in exact f32); train with precision='f32'" % self.precision)
+        rays_d, angle, z_c = self.sampler(xs, ys, perturb, noise)
+        wstream = self.pw.pack(flat_params.detach())
+        raw_c = self._eval_train(flat_params, wstream, rays_d, angle, z_c)
+        rgb_c, depth_c, acc_c, w_c, _, _ = ops.composite(raw_c, z_c, self.white_bkgd)
+        hs = ops.sample_pdf(None, w_c.detach(), self.u_det if u is None else u, z_merge=z_c, want_inds=False, from_coarse=True, want_rank=True)
+        raw_f = self._eval_train(flat_params, wstream, rays_d, angle, hs["samples"])
+        rgb, depth, acc, weights, disp, var = ops.composite_merged(raw_f, raw_c, hs["merge_rank"], hs["z_sorted"], self.white_bkgd)      # cat(samples, z_coarse) order
+        coarse = dict(rgb=rgb_c, depth=depth_c, weights=w_c, raw=raw_c, samples=hs["samples"], z_sorted=hs["z_sorted"], merge_rank=hs["merge_rank"])
+        return dict(rgb=rgb, depth=depth, acc=acc, disp=disp, weights=weights, var=var, z_coarse=z_c, z_fine=hs["z_sorted"], z_samples=hs["samples"],
+                    coarse=coarse, rays_d=rays_d)
 
     # ------------------------------------------------------------------------------------------------ HIP graph
     def capture(self, n_rays, perturb=0.0, repack=True, reuse_coarse=None):
