@@ -771,6 +771,77 @@ typedef struct ucnerf_image_eval_params ucnerf_image_eval_params;
 int ucnerf_image_eval(const ucnerf_image_eval_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f3   the cascade depth loss on the device -- network/mvs_models.py:512-529 (cas_mvsnet_loss) without its boolean-mask indexing: est[mask],
+ *      gt[mask] and w[w > 0] compact, compaction needs the element counts on the host, and a step that reads the device back cannot be captured
+ *      into a graph.  Here the counts stay on the device.  (Added to ABI v6; nothing above moved.  Structs declared with a tag: mirrored in
+ *      _lib.ADDED_STRUCTS.)
+ *
+ *   per stage s (1 to 3 stages, est / gt / w [n[s]] each):
+ *     valid(i)   = gt[i] > 0  (a NaN is not valid);   positive(j) = w[j] > 0
+ *     the k-th valid element in row-major order is paired with the k-th positive weight in row-major order -- NOT with the weight at its
+ *     own pixel (the two coincide only where both maps are positive at exactly the same pixels)
+ *     term(i)    = smooth-L1, beta 1, of d = est[i] - gt[i]:  0.5 d^2 for |d| < 1, |d| - 0.5 otherwise
+ *     stage_loss[s] = sum over valid i of term(i) * weight(i)  /  float(count[s]),   count[s] = the number of valid elements
+ *   total = ((0 + stage_w[0] stage_loss[0]) + stage_w[1] stage_loss[1]) + ...      (the reference's order)
+ *   with_weight == 0: the weights are not read (w may be NULL) and wpair is 1 on the valid elements.
+ *
+ *   Edge semantics
+ *     - no valid element: stage_loss[s] = 0 / 0 = NaN, as torch's mean of an empty tensor; the NaN propagates into total.
+ *     - with weights on, count[s] != the number of positive weights (torch raises there, which a device cannot do without a read-back):
+ *       stage_loss[s] = NaN, wpair = NaN on the valid elements (so the gradients are NaN there too), and bit s of *status is set.  *status is a
+ *       caller-provided device word, only ever OR-ed into (sticky); it may be NULL.
+ *       THE ONE DIFFERENCE FROM TORCH: where exactly one of the two counts is 1, torch broadcasts the single value; this is a mismatch here.
+ *     - n_stages outside 1..3, an n[s] outside 1..2^30, a NULL required pointer: UCNERF_EINVAL (a stage of zero elements is NOT an empty batch:
+ *       its loss would be NaN, which only a launch can write).
+ *
+ *   One launch of ONE workgroup of 1024 threads, the stages one after the other, so that `total` is formed in the same launch by the thread
+ *   that holds the stage losses: no workgroup waits for, polls or signals another.  Per stage: wave v owns the contiguous run of
+ *   ceil(ceil(n / 64) / 16) tiles of 64 elements from v times that on (contiguous runs keep ranks in row-major order; a tile is one coalesced
+ *   load); pass 1 counts valid elements and positive weights per wave (ballot + popcount: integers), exclusive offsets over the 16 waves from
+ *   LDS; pass 2 writes the positive weights to workspace[rank]; a barrier makes the workgroup's own stores visible to itself; pass 3 reads
+ *   workspace[rank] at the valid elements, forms the terms, writes wpair and sums in a fixed order -- per lane over its tiles, a shuffle tree
+ *   over the wave, a pairwise tree over the 16 waves.  The order depends on the shapes alone: the same inputs give the same bits.
+ *   Bound: latency (one CU; about 1 MB read at the reference's 256 x 320 stage sizes).
+ *
+ *   ucnerf_cas_loss_bwd: elementwise, grid over all stages, every element of g_est written (no zero fill):
+ *     g_est[s][i] = valid(i) ? ((g_total[0] * stage_w[s] (+ g_stage[s])) / float(count[s])) * wpair[s][i] * clamp(est - gt, -1, 1) : 0
+ *   g_total and count are read on the device; the division is a division (torch's mean backward), not a multiplication by a reciprocal. */
+int64_t ucnerf_cas_loss_workspace_floats(int32_t n_stages, const int32_t* n_host);   /* sum of n[s]; < 0 on a bad argument */
+
+struct ucnerf_cas_loss_params {
+    int32_t n_stages;          /* 1..3 */
+    int32_t with_weight;
+    int32_t n[3];              /* elements per stage */
+    float stage_w[3];          /* the reference: 0.5, 1, 2 by the stage number in the key */
+    const float* est[3];       /* [n[s]] */
+    const float* gt[3];        /* [n[s]] */
+    const float* w[3];         /* [n[s]]; not read (may be NULL) when with_weight == 0 */
+    float* workspace;          /* ucnerf_cas_loss_workspace_floats(n_stages, n) floats; not used (may be NULL) when with_weight == 0 */
+    float* total;              /* [1] */
+    float* stage_loss;         /* [n_stages] */
+    int32_t* count;            /* [n_stages] valid elements */
+    float* wpair[3];           /* [n[s]] the weight each element was paired with, 0 where it is not valid; all NULL: not written */
+    int32_t* status;           /* [1] sticky mismatch bits, or NULL */
+};
+typedef struct ucnerf_cas_loss_params ucnerf_cas_loss_params;
+int ucnerf_cas_loss_fwd(const ucnerf_cas_loss_params* p, void* stream);
+
+struct ucnerf_cas_loss_bwd_params {
+    int32_t n_stages;
+    int32_t n[3];
+    float stage_w[3];
+    const float* est[3];       /* the forward's inputs ... */
+    const float* gt[3];
+    const float* wpair[3];     /* ... and outputs */
+    const int32_t* count;      /* [n_stages] */
+    const float* g_total;      /* [1] */
+    const float* g_stage;      /* [n_stages] upstream gradient of stage_loss, or NULL */
+    float* g_est[3];           /* [n[s]] out */
+};
+typedef struct ucnerf_cas_loss_bwd_params ucnerf_cas_loss_bwd_params;
+int ucnerf_cas_loss_bwd(const ucnerf_cas_loss_bwd_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * a10  one fused render pass -- network/renderer.py:215-255 (rendering) with the projection of
  *      utils/utils.py:716-724 in front: rays + depths -> world points -> stage coordinates -> features ->
  *      PE + MLP -> composite.  Source views = pose entries 1..V of the reference's pose_ref

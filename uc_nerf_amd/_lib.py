@@ -168,6 +168,16 @@ class ImageEvalParams(C.Structure):
     _fields_ = [("n", i32), ("H", i32), ("W", i32), ("no_ssim", i32), ("gt", vp), ("pred", vp), ("workspace", vp), ("out", vp)]
 
 
+class CasLossParams(C.Structure):
+    _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
+                ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
+
+
+class CasLossBwdParams(C.Structure):
+    _fields_ = [("n_stages", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("wpair", vp * 3), ("count", vp),
+                ("g_total", vp), ("g_stage", vp), ("g_est", vp * 3)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -205,7 +215,8 @@ STRUCTS = {
 # checked against the library's sizeof() at load time like the others
 ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams,
                  "ucnerf_composite_merged_params": CompositeMergedParams, "ucnerf_depth_eval_params": DepthEvalParams,
-                 "ucnerf_image_eval_params": ImageEvalParams, "ucnerf_composite_merged_bwd_params": CompositeMergedBwdParams}
+                 "ucnerf_image_eval_params": ImageEvalParams, "ucnerf_composite_merged_bwd_params": CompositeMergedBwdParams,
+                 "ucnerf_cas_loss_params": CasLossParams, "ucnerf_cas_loss_bwd_params": CasLossBwdParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -274,6 +285,10 @@ SYMBOLS = {
     "ucnerf_eval_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_depth_eval": (C.c_int, [_P, _P]),
     "ucnerf_image_eval": (C.c_int, [_P, _P]),
+    # the cascade depth loss on the device (additive to ABI v6)
+    "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
+    "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),
+    "ucnerf_cas_loss_bwd": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

@@ -440,6 +440,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_render_bwd_params); SZ(ucnerf_cl_sources); SZ(ucnerf_cl_grads); SZ(ucnerf_build_rays_test_params);
     SZ(ucnerf_depth_hypotheses_params); SZ(ucnerf_build_rays_train_params); SZ(ucnerf_composite_merged_params);
     SZ(ucnerf_depth_eval_params); SZ(ucnerf_image_eval_params); SZ(ucnerf_composite_merged_bwd_params);
+    SZ(ucnerf_cas_loss_params); SZ(ucnerf_cas_loss_bwd_params);
 #undef SZ
     return -1;
 }

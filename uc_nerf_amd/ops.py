@@ -1444,6 +1444,113 @@ def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=
     return out
 
 
+# ------------------------------------------------------------------------------------------------ f3: the cascade depth loss
+# one sticky status word per device (bit s: stage s of a cas_loss call had a valid count different from its positive-weight count), allocated
+# once and kept for the life of the process: captured graphs hold its address
+_loss_words = {}
+
+
+def _loss_word(device=None):
+    idx = _cur_dev() if device is None or torch.device(device).index is None else torch.device(device).index
+    w = _loss_words.get(idx)
+    if w is None:
+        w = _loss_words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return w
+
+
+def loss_status(clear=False, device=None):
+    """The cascade loss's status word of `device` (default: the current one) as an int: bit s set = stage s of some `cas_loss` call since the last
+    clear had a number of valid depths different from its number of positive weights (its loss was NaN).  SYNCHRONISES (reads the word back);
+    clear=True also zeroes it afterwards."""
+    w = _loss_word(device)
+    v = int(w.item())
+    if clear:
+        w.zero_()
+    return v
+
+
+def loss_status_clear(device=None):
+    """Enqueues a clear of the status word on the current stream (no synchronisation)."""
+    _loss_word(device).zero_()
+
+
+class _CasLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stage_weights, with_weight, status, n_stages, *tensors):
+        ests, gts, ws = tensors[:n_stages], tensors[n_stages:2 * n_stages], tensors[2 * n_stages:]
+        dev = ests[0].device
+        sizes = [e.numel() for e in ests]
+        p = L.CasLossParams()
+        p.n_stages, p.with_weight = n_stages, int(with_weight)
+        head = torch.empty(1 + n_stages, device=dev)                      # total | stage losses
+        count = torch.empty(n_stages, dtype=torch.int32, device=dev)
+        wpair = torch.empty(sum(sizes), device=dev)
+        work = torch.empty(sum(sizes), device=dev) if with_weight else None
+        at = 0
+        for s in range(n_stages):
+            p.n[s], p.stage_w[s] = sizes[s], float(stage_weights[s])
+            p.est[s], p.gt[s], p.w[s] = _ptr(ests[s]), _ptr(gts[s]), _ptr(ws[s]) if with_weight else 0
+            p.wpair[s] = wpair.data_ptr() + 4 * at
+            at += sizes[s]
+        p.workspace, p.total, p.stage_loss, p.count, p.status = _ptr(work), head.data_ptr(), head.data_ptr() + 4, _ptr(count), _ptr(status)
+        _launch("ucnerf_cas_loss_fwd", p, dev)
+        ctx.save_for_backward(wpair, count, *ests, *gts)
+        ctx.n_stages, ctx.n_inputs, ctx.stage_weights = n_stages, len(tensors), tuple(float(x) for x in stage_weights)
+        total, stage_loss = head[0], head[1:]
+        ctx.mark_non_differentiable(count)
+        ctx.set_materialize_grads(False)                                  # (an unused output's gradient arrives as None, not as a zero fill)
+        return total, stage_loss, count
+
+    @staticmethod
+    def backward(ctx, g_total, g_stage, _g_count):
+        n = ctx.n_stages
+        wpair, count = ctx.saved_tensors[:2]
+        ests, gts = ctx.saved_tensors[2:2 + n], ctx.saved_tensors[2 + n:]
+        dev = wpair.device
+        g_total = _f32(g_total, "g_total") if g_total is not None else torch.zeros(1, device=dev)
+        g_stage = _f32(g_stage, "g_stage_loss") if g_stage is not None else None
+        p = L.CasLossBwdParams()
+        p.n_stages = n
+        g_all = torch.empty_like(wpair)
+        grads, at = [], 0
+        for s in range(n):
+            k = ests[s].numel()
+            p.n[s], p.stage_w[s] = k, ctx.stage_weights[s]
+            p.est[s], p.gt[s], p.wpair[s], p.g_est[s] = _ptr(ests[s]), _ptr(gts[s]), wpair.data_ptr() + 4 * at, g_all.data_ptr() + 4 * at
+            grads.append(g_all[at:at + k].view(ests[s].shape))
+            at += k
+        p.count, p.g_total, p.g_stage = _ptr(count), _ptr(g_total), _ptr(g_stage)
+        _launch("ucnerf_cas_loss_bwd", p, dev)
+        return (None, None, None, None) + tuple(grads) + (None,) * (ctx.n_inputs - n)
+
+
+def cas_loss(ests, gts, ws, stage_weights, with_weight=True, status=None):
+    """The cascade depth loss (network/mvs_models.py:512-529) of up to three stages in ONE launch, nothing read back: per stage the smooth-L1 term
+    of the k-th valid depth (gt > 0, row-major order) times the k-th positive weight (w > 0, row-major order), summed and divided by the valid
+    count; total = sum of stage_weights[s] * stage loss.  ests / gts / ws: per stage, float32 tensors of one size each on one device.
+    Returns (total 0-d, stage_loss [n_stages], count [n_stages] int32) on the device; the backward is one launch and gives gradients for the
+    `ests` only.  A stage without a valid element is NaN (torch's mean of nothing).  A stage whose valid count differs from its positive-weight
+    count is NaN and sets bit s of `status` (a one-element int32 device tensor; default: the device's own word, see `loss_status`) -- torch
+    raises there, or broadcasts where one of the counts is 1: that broadcast is NOT reproduced, it counts as a mismatch.
+    with_weight=False: the weights are ignored (`ws` may be None)."""
+    n = len(ests)
+    if not 1 <= n <= 3 or len(gts) != n or (with_weight and (ws is None or len(ws) != n)) or len(stage_weights) != n:
+        raise RuntimeError("uc_nerf_amd.cas_loss: 1 to 3 stages, each with est, gt%s and a stage weight" % (", w" if with_weight else ""))
+    ests = [_f32(e, "est") for e in ests]
+    dev = ests[0].device
+    gts = [_f32(g.detach(), "gt") for g in gts]
+    ws = [_f32(w.detach(), "w") for w in ws] if with_weight else []
+    for s in range(n):
+        others = [gts[s]] + ([ws[s]] if with_weight else [])
+        if ests[s].numel() == 0 or any(t.numel() != ests[s].numel() or t.device != dev for t in others + [ests[s]]):
+            raise RuntimeError("uc_nerf_amd.cas_loss: stage %d: est, gt and w must hold the same (non-zero) number of elements on one device" % s)
+    if status is None:
+        status = _loss_word(dev)
+    elif not (torch.is_tensor(status) and status.is_cuda and status.dtype == torch.int32 and status.numel() == 1 and status.device == dev):
+        raise RuntimeError("uc_nerf_amd.cas_loss: status must be a one-element int32 tensor on the estimates' device")
+    return _CasLoss.apply(tuple(stage_weights), bool(with_weight), status, n, *ests, *gts, *ws)
+
+
 # ------------------------------------------------------------------------------------------------ e1
 def _eval_workspace(n, H, W, dev):
     floats = L.lib().ucnerf_eval_workspace_floats(n, H, W)

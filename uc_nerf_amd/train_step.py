@@ -49,7 +49,7 @@ class BatchShard:
 
 
 def sharded_training_loss(rgb, depth_pred, target_s, target_depths, target_weights, patch_dpt, mvs_outputs, depth_sparse_ms, weight_ms,
-                          shard, smooth_loss=None, edge_loss=None, mvs_term=None):
+                          shard, smooth_loss=None, edge_loss=None, mvs_term=None, mvs_on_device=False):
     """This rank's share of the loss of train.py:164-188; all arguments are the rank's LOCAL rows in `shard.index` order
     (`patch_dpt`: rows `shard.patch_ids`, `target_depths/weights`: rows `shard.depth_ids`).  Summed over the ranks it is the
     single-process loss, and so are its gradients.  Returns (weighted local loss, dict of weighted local terms)."""
@@ -67,8 +67,9 @@ def sharded_training_loss(rgb, depth_pred, target_s, target_depths, target_weigh
     nerf_depth = (torch.mean(((depth_pred[n_loc - nd:] - target_depths) ** 2) * target_weights) * (nd / tot["depth"])) if nd else zero
     img = L.img2mse(rgb, target_s) * (n_loc / tot["rays"]) if n_loc else zero
     # (mvs_term: the cascade depth loss already evaluated -- its boolean-mask indexing reads sizes back to the host, which a graph capture does
-    #  not admit; it depends on nothing the renderer produces)
-    mvs = mvs_term if mvs_term is not None else L.cas_mvsnet_loss(mvs_outputs, depth_sparse_ms, weight_ms)[0]
+    #  not admit; it depends on nothing the renderer produces.  mvs_on_device: the same term from L.cas_mvsnet_loss_device, which reads nothing
+    #  back and may therefore sit inside a captured step)
+    mvs = mvs_term if mvs_term is not None else (L.cas_mvsnet_loss_device if mvs_on_device else L.cas_mvsnet_loss)(mvs_outputs, depth_sparse_ms, weight_ms)[0]
     mvs = mvs / shard.world                                                  # replicated term: every rank holds all of it
     loss = nerf_depth * 0.05 + mvs * 0.05 + smooth * 0.05 + scale_inv * 0.008 + img * 5.0
     return loss, {"img_loss": img, "loss_nerf_depth": nerf_depth, "loss_mvs": mvs, "smooth_loss": smooth,

@@ -3,7 +3,8 @@
 `cas_mvsnet_loss` (`network/mvs_models.py:491-529`), plus the weighting of `train.py:164-188` as one function.
 
 These are reductions over at most a few thousand values per step; they are plain torch expressions on the tensors' own
-device (autograd included), not kernels.  Same names, argument orders and results as the reference.
+device (autograd included), not kernels.  Same names, argument orders and results as the reference.  The one exception is
+`cas_mvsnet_loss_device`: the cascade term as a kernel, because its torch form reads element counts back to the host.
 """
 import torch
 import torch.nn as nn
@@ -93,15 +94,45 @@ def cas_mvsnet_loss(inputs, depth_gt_ms, weight_ms, with_weight=True, mvs_type=0
     return total, depth_loss
 
 
+def cas_mvsnet_loss_device(inputs, depth_gt_ms, weight_ms, with_weight=True, mvs_type=0, status=None, **kwargs):
+    """`cas_mvsnet_loss` for estimates on a ROCm device with NO host read: same arguments, same handling of the keys, same pair
+    (total, the last stage's loss), from one kernel launch (`ops.cas_loss`; its backward is one more).  The boolean-mask indexing above compacts,
+    which needs the element counts on the host -- three stream drains a step, and a step that a HIP graph cannot capture; here the k-th valid depth
+    meets the k-th positive weight through a rank formed on the device, and the valid count may change from one graph replay to the next.
+    Differences: a stage whose valid count differs from its positive-weight count is NaN and sets a bit of `status` (default: the device's word,
+    `loss_status()`), where torch raises -- or broadcasts when one count is 1, which is NOT reproduced; at most three stages."""
+    from .. import ops
+    stage_w = [0.5, 1.0, 2.0]
+    keys = [k for k in inputs.keys() if "stage" in k]
+    if not keys:
+        return 0, None
+    ests = [inputs[k]["depth"] for k in keys]
+    gts = [depth_gt_ms[k].to(e.device, non_blocking=True) for k, e in zip(keys, ests)]
+    ws = [weight_ms[k].to(e.device, non_blocking=True) for k, e in zip(keys, ests)] if with_weight else None
+    total, stage_loss, _ = ops.cas_loss(ests, gts, ws, [stage_w[int(k.replace("stage", "")) - 1] for k in keys], with_weight=with_weight, status=status)
+    return total, stage_loss[-1]
+
+
+def loss_status(clear=False, device=None):
+    """The sticky status word of `cas_mvsnet_loss_device` (bit s: stage s had mismatched counts).  Synchronises; see `ops.loss_status`."""
+    from .. import ops
+    return ops.loss_status(clear=clear, device=device)
+
+
+def loss_status_clear(device=None):
+    from .. import ops
+    ops.loss_status_clear(device=device)
+
+
 def training_loss(rgb, depth_pred, target_s, target_depths, target_weights, patch_dpt, mvs_outputs, depth_sparse_ms, weight_ms,
-                  n_rays, patch_num, patch_size, smooth_loss=None, edge_loss=None):
+                  n_rays, patch_num, patch_size, smooth_loss=None, edge_loss=None, mvs_on_device=False):
     """The loss of `train.py:164-188`.  The batch is [patch rays (patch_num * patch_size^2) | random rays | rays_depth rays
     from `n_rays` on]; `patch_dpt` is the DPT prior at the patch pixels [patch_num, patch_size, patch_size, 1].
-    Returns (loss, parts)."""
+    Returns (loss, parts).  mvs_on_device=True: the cascade term through `cas_mvsnet_loss_device` (no host read)."""
     smooth_loss = smooth_loss or EdgePreservingSmoothnessLoss()
     edge_loss = edge_loss or GradientLoss()
     patch_pts = patch_num * patch_size * patch_size
-    loss_mvs, _ = cas_mvsnet_loss(mvs_outputs, depth_sparse_ms, weight_ms)
+    loss_mvs, _ = (cas_mvsnet_loss_device if mvs_on_device else cas_mvsnet_loss)(mvs_outputs, depth_sparse_ms, weight_ms)
     patch_depth = depth_pred[:patch_pts].reshape(-1, patch_size, patch_size)
     smooth = smooth_loss(patch_depth[:patch_num // 2, ...], patch_dpt[:patch_num // 2, ...])
     loss_nerf_depth = torch.mean(((depth_pred[n_rays:] - target_depths) ** 2) * target_weights)
