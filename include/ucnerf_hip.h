@@ -771,6 +771,75 @@ typedef struct ucnerf_image_eval_params ucnerf_image_eval_params;
 int ucnerf_image_eval(const ucnerf_image_eval_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * e2   a whole validation image on the device -- train.py:274-288 (the reference pulls every rendered chunk to the host, concatenates, clamps and
+ *      permutes there) and utils/utils.py:58-77 (visualize_depth: numpy normalisation, cv2.applyColorMap, PIL, ToTensor).  Here a chunk is
+ *      written straight into the image planes the metrics above read, the depth range is kept in a two-word cell on the device, and the
+ *      depth picture is one launch.  (Added to ABI v6; nothing above moved.  Structs declared with a tag: mirrored in _lib.ADDED_STRUCTS.)
+ *      No entry point synchronises the stream or reads anything back; all stores are plain vector stores and global atomics.
+ *
+ *   The range cell: two uint32 words in DEVICE memory, owned by the caller, holding the smallest and the largest order key folded in so far
+ *   (key(f) = bits ^ 0xffffffff for a negative f, bits ^ 0x80000000 otherwise: unsigned order is float order, -0.0 right below +0.0).  What is
+ *   folded is nan_to_num(depth) as numpy's float32: NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX.  One workgroup reduces the pixels it covers
+ *   (ucnerf_image_group_pixels of them) and issues one atomicMin and one atomicMax.  ucnerf_minmax_reset empties the cell: (0xffffffff, 0),
+ *   which reads back as (NaN, NaN).  ucnerf_minmax_read decodes the cell into two floats (min, max) on the device.  The values equal numpy's
+ *   min / max of nan_to_num bit for bit, except that the zero numpy returns may carry the other sign (-0.0 == +0.0).
+ *
+ *   ucnerf_image_put: one rendered chunk into the image.  Chunk pixel i is image pixel q = first_pixel + i of the flattened H x W grid:
+ *     rgb_chw[c * pixels + q] = min(max(rgb[i][c], 0), 1) by comparison, torch.clamp's semantics: a NaN stays NaN, -0.0 stays -0.0;
+ *     depth_hw[q] = depth[i], unchanged;  the chunk's depths are folded into `minmax` when that is non-NULL.
+ *     Chunks may arrive in any order; chunks that overlap leave the later launch's values.  UCNERF_EINVAL, checked on the host before
+ *     anything is launched: a negative n, first_pixel or pixels, first_pixel + n > pixels (an overrun), a NULL required array.  n == 0 is
+ *     success, nothing launched.
+ *   ucnerf_depth_minmax: the same fold for any map of `count` elements (a ground-truth depth that did not come through ucnerf_image_put).
+ *   ucnerf_depth_colormap: visualize_depth's arithmetic, in float32 and rounding for rounding as numpy does it:
+ *     x = nan_to_num(depth);  t = (x - mi) / d (an IEEE division);  v = 255 * t (a second rounding, never fused with the first);
+ *     index = uint8(v), truncated toward zero;  color[c * count + i] = float(table[index][c]) / 255 (an IEEE division: what ToTensor does).
+ *     The range comes from the cell (minmax non-NULL; utils/utils.py:66-68): mi = min, d = (max - min) + float32(1e-8), all in float32 --
+ *     or from the host (minmax NULL; the reference's minmax= argument, a pair of Python floats): mi = float32(range_host[0]),
+ *     d = float32(range_host[1] - range_host[0] + 1e-8) formed in double.
+ *     THE ONE PLACE THIS IS STRICTER THAN NUMPY: the uint8 conversion of a NaN or of a value outside 0 .. 255 is undefined there (and differs
+ *     between machines); here a NaN gives 0, a v below 0 gives 0 and a v above 255 gives 255.
+ *     Channel c is column c of the table as it stands.  The reference hands cv2's B, G, R rows to PIL as if they were R, G, B, so with a table
+ *     in OpenCV's column order channel 0 of the picture is OpenCV's blue -- that is what the reference shows, and it is kept.
+ *     Either of index / color may be NULL (not both); table is read only for color. */
+int32_t ucnerf_image_group_pixels(void);   /* pixels one workgroup of the three kernels covers (1024) */
+int ucnerf_minmax_reset(uint32_t* minmax, void* stream);
+int ucnerf_minmax_read(const uint32_t* minmax, float* out, void* stream);   /* out [2] = (min, max) */
+
+struct ucnerf_image_put_params {
+    int32_t n;                 /* pixels of the chunk */
+    int32_t first_pixel;       /* flattened row-major index of the chunk's first pixel */
+    int32_t pixels;            /* H * W */
+    const float* rgb;          /* [n,3] */
+    const float* depth;        /* [n] */
+    float* rgb_chw;            /* [3, pixels] */
+    float* depth_hw;           /* [pixels] */
+    uint32_t* minmax;          /* [2] range cell, or NULL */
+};
+typedef struct ucnerf_image_put_params ucnerf_image_put_params;
+int ucnerf_image_put(const ucnerf_image_put_params* p, void* stream);
+
+struct ucnerf_depth_minmax_params {
+    int32_t count;
+    const float* depth;        /* [count] */
+    uint32_t* minmax;          /* [2] range cell, folded into (reset it first) */
+};
+typedef struct ucnerf_depth_minmax_params ucnerf_depth_minmax_params;
+int ucnerf_depth_minmax(const ucnerf_depth_minmax_params* p, void* stream);
+
+struct ucnerf_depth_colormap_params {
+    int32_t count;
+    double range_host[2];      /* (mi, ma) as the caller's Python floats; read when minmax is NULL */
+    const float* depth;        /* [count] */
+    const uint32_t* minmax;    /* [2] range cell, or NULL */
+    const uint8_t* table;      /* [256,3] colours, or NULL when color is NULL */
+    uint8_t* index;            /* [count] out, or NULL */
+    float* color;              /* [3, count] out, or NULL */
+};
+typedef struct ucnerf_depth_colormap_params ucnerf_depth_colormap_params;
+int ucnerf_depth_colormap(const ucnerf_depth_colormap_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3   the cascade depth loss on the device -- network/mvs_models.py:512-529 (cas_mvsnet_loss) without its boolean-mask indexing: est[mask],
  *      gt[mask] and w[w > 0] compact, compaction needs the element counts on the host, and a step that reads the device back cannot be captured
  *      into a graph.  Here the counts stay on the device.  (Added to ABI v6; nothing above moved.  Structs declared with a tag: mirrored in

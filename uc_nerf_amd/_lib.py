@@ -178,6 +178,18 @@ class CasLossBwdParams(C.Structure):
                 ("g_total", vp), ("g_stage", vp), ("g_est", vp * 3)]
 
 
+class ImagePutParams(C.Structure):
+    _fields_ = [("n", i32), ("first_pixel", i32), ("pixels", i32), ("rgb", vp), ("depth", vp), ("rgb_chw", vp), ("depth_hw", vp), ("minmax", vp)]
+
+
+class DepthMinmaxParams(C.Structure):
+    _fields_ = [("count", i32), ("depth", vp), ("minmax", vp)]
+
+
+class DepthColormapParams(C.Structure):
+    _fields_ = [("count", i32), ("range_host", C.c_double * 2), ("depth", vp), ("minmax", vp), ("table", vp), ("index", vp), ("color", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -216,7 +228,9 @@ STRUCTS = {
 ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucnerf_build_rays_train_params": BuildRaysTrainParams,
                  "ucnerf_composite_merged_params": CompositeMergedParams, "ucnerf_depth_eval_params": DepthEvalParams,
                  "ucnerf_image_eval_params": ImageEvalParams, "ucnerf_composite_merged_bwd_params": CompositeMergedBwdParams,
-                 "ucnerf_cas_loss_params": CasLossParams, "ucnerf_cas_loss_bwd_params": CasLossBwdParams}
+                 "ucnerf_cas_loss_params": CasLossParams, "ucnerf_cas_loss_bwd_params": CasLossBwdParams,
+                 "ucnerf_image_put_params": ImagePutParams, "ucnerf_depth_minmax_params": DepthMinmaxParams,
+                 "ucnerf_depth_colormap_params": DepthColormapParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -289,6 +303,13 @@ SYMBOLS = {
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),
     "ucnerf_cas_loss_bwd": (C.c_int, [_P, _P]),
+    # a whole validation image on the device (additive to ABI v6)
+    "ucnerf_image_group_pixels": (C.c_int32, []),
+    "ucnerf_minmax_reset": (C.c_int, [_P, _P]),
+    "ucnerf_minmax_read": (C.c_int, [_P, _P, _P]),
+    "ucnerf_image_put": (C.c_int, [_P, _P]),
+    "ucnerf_depth_minmax": (C.c_int, [_P, _P]),
+    "ucnerf_depth_colormap": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

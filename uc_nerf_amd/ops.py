@@ -1604,6 +1604,121 @@ def image_eval(gt, pred, ssim=True):
     return dict(mse=out[:, 0], psnr=out[:, 1], ssim=out[:, 2], gt_max=out[:, 3], packed=out)
 
 
+# ------------------------------------------------------------------------------------------------ e2
+def image_group_pixels():
+    """Pixels one workgroup of the image kernels covers (and folds into one atomicMin / atomicMax)."""
+    return int(L.lib().ucnerf_image_group_pixels())
+
+
+def _is_cell(t):
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.numel() == 2 and t.is_contiguous()
+
+
+def minmax_reset(cell=None, device=None):
+    """Empties a range cell (a new one on `device` when none is given) and returns it: an int32 [2] device tensor holding the order keys of the
+    smallest and largest nan_to_num(depth) folded in so far.  `minmax_value` decodes it; an empty cell decodes to (NaN, NaN)."""
+    if cell is None:
+        if device is None:
+            raise RuntimeError("uc_nerf_amd.minmax_reset: a cell or a device")
+        cell = torch.empty(2, dtype=torch.int32, device=device)
+    if not _is_cell(cell):
+        raise RuntimeError("uc_nerf_amd: a range cell is a contiguous int32 [2] tensor on a ROCm device (minmax_reset makes one)")
+    with _on(cell.device):
+        L.check(L.lib().ucnerf_minmax_reset(_ptr(cell), C.c_void_p(_stream())), "ucnerf_minmax_reset")
+    return cell
+
+
+def minmax_value(cell):
+    """The cell's range as a float32 [2] device tensor (min, max); one tiny launch, nothing is read back."""
+    if not _is_cell(cell):
+        raise RuntimeError("uc_nerf_amd: a range cell is a contiguous int32 [2] tensor on a ROCm device (minmax_reset makes one)")
+    out = torch.empty(2, device=cell.device)
+    with _on(cell.device):
+        L.check(L.lib().ucnerf_minmax_read(_ptr(cell), _ptr(out), C.c_void_p(_stream())), "ucnerf_minmax_read")
+    return out
+
+
+def image_put(rgb, depth, first_pixel, rgb_chw, depth_hw, cell=None):
+    """One rendered chunk into the image planes, in place: rgb [n,3], depth [n] -> rgb_chw [3,H,W] (clamped to [0,1] as torch.clamp does: NaN and
+    -0.0 stay) and depth_hw [H,W] at pixels first_pixel .. first_pixel + n - 1 of the flattened grid; with `cell` the chunk's depth range is folded
+    into it in the same launch.  An overrun of the image raises."""
+    rgb, depth = _f32(rgb, "rgb"), _f32(depth, "depth")
+    dev = rgb.device
+    n = depth.numel()
+    if rgb.numel() != 3 * n or rgb.shape[-1] != 3:
+        raise RuntimeError("uc_nerf_amd.image_put: rgb must be [n,3] and depth [n], got %s and %s" % (tuple(rgb.shape), tuple(depth.shape)))
+    for t, name in ((rgb_chw, "rgb_chw"), (depth_hw, "depth_hw")):
+        _dev(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or depth.device != dev:
+            raise RuntimeError("uc_nerf_amd.image_put: %s must be a contiguous float32 tensor on the chunk's device" % name)
+    pixels = depth_hw.numel()
+    if rgb_chw.numel() != 3 * pixels or rgb_chw.shape[0] != 3:
+        raise RuntimeError("uc_nerf_amd.image_put: rgb_chw must be [3,H,W] for depth_hw [H,W], got %s and %s" % (tuple(rgb_chw.shape), tuple(depth_hw.shape)))
+    if cell is not None and not (_is_cell(cell) and cell.device == dev):
+        raise RuntimeError("uc_nerf_amd.image_put: cell must be a range cell on the chunk's device")
+    p = L.ImagePutParams()
+    p.n, p.first_pixel, p.pixels = n, int(first_pixel), pixels
+    p.rgb, p.depth, p.rgb_chw, p.depth_hw, p.minmax = _ptr(rgb), _ptr(depth), _ptr(rgb_chw), _ptr(depth_hw), _ptr(cell)
+    _launch("ucnerf_image_put", p, dev)
+
+
+def depth_minmax(depth, cell=None):
+    """min and max of nan_to_num(depth) as a float32 [2] device tensor.  With `cell` the map is folded into that cell (not reset first) and the
+    cell's range so far is returned."""
+    depth = _f32(depth, "depth")
+    dev = depth.device
+    if cell is None:
+        cell = minmax_reset(device=dev)
+    elif not (_is_cell(cell) and cell.device == dev):
+        raise RuntimeError("uc_nerf_amd.depth_minmax: cell must be a range cell on the map's device")
+    p = L.DepthMinmaxParams()
+    p.count, p.depth, p.minmax = depth.numel(), _ptr(depth), _ptr(cell)
+    _launch("ucnerf_depth_minmax", p, dev)
+    return minmax_value(cell)
+
+
+def colormap_table(table, device):
+    """A 256 x 3 uint8 colour table (numpy array or tensor) as a contiguous device tensor."""
+    t = table if torch.is_tensor(table) else torch.as_tensor(table)
+    if t.dtype != torch.uint8 or tuple(t.shape) != (256, 3):
+        raise RuntimeError("uc_nerf_amd: a colour table is 256 x 3 uint8, got %s %s" % (t.dtype, tuple(t.shape)))
+    return t.to(device).contiguous()
+
+
+def depth_colormap(depth, table=None, minmax=None, want_index=True, want_color=True):
+    """visualize_depth's arithmetic (utils/utils.py:65-76) on the device: depth (any shape, float32) -> (index uint8 of depth's shape or None,
+    color float32 [3, *depth.shape] or None).  `minmax`: None -- the map's own range (one more launch); a range cell; or a pair of Python
+    floats (the reference's minmax= argument).  `table`: 256 x 3 uint8 on the device (colormap_table), needed for the colour image.
+    The uint8 conversion is defined where numpy's is not: NaN -> 0, below 0 -> 0, above 255 -> 255."""
+    depth = _f32(depth, "depth")
+    dev = depth.device
+    p = L.DepthColormapParams()
+    p.count, p.depth = depth.numel(), _ptr(depth)
+    cell = None
+    if minmax is None:
+        cell = minmax_reset(device=dev)
+        q = L.DepthMinmaxParams()
+        q.count, q.depth, q.minmax = depth.numel(), _ptr(depth), _ptr(cell)
+        _launch("ucnerf_depth_minmax", q, dev)
+    elif torch.is_tensor(minmax):
+        if not (_is_cell(minmax) and minmax.device == dev):
+            raise RuntimeError("uc_nerf_amd.depth_colormap: a tensor minmax must be a range cell on the map's device (a pair of floats otherwise)")
+        cell = minmax
+    else:
+        p.range_host[0], p.range_host[1] = float(minmax[0]), float(minmax[1])
+    p.minmax = _ptr(cell)
+    if want_color:
+        if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.uint8 and tuple(table.shape) == (256, 3)
+                and table.is_contiguous() and table.device == dev):
+            raise RuntimeError("uc_nerf_amd.depth_colormap: table must be a contiguous 256 x 3 uint8 tensor on the map's device (colormap_table)")
+        p.table = _ptr(table)
+    index = torch.empty(depth.shape, dtype=torch.uint8, device=dev) if want_index else None
+    color = torch.empty((3,) + tuple(depth.shape), device=dev) if want_color else None
+    p.index, p.color = _ptr(index), _ptr(color)
+    _launch("ucnerf_depth_colormap", p, dev)
+    return index, color
+
+
 # ------------------------------------------------------------------------------------------------ a10
 class RenderPass:
     """Pre-bound arguments of ucnerf_render_fused_fwd for one scene; call it with (rays_d, z).

@@ -2,7 +2,8 @@
 `get_rays_mvs_coord`, `get_rays_with_random_patches`), `get_ndc_coordinate`, `sample_points_uniform`, the two ray
 builders (`build_rays`, `build_rays_test`), the two halves of the feature gather (`index_point_feature`,
 `build_color_volume`) and the small helpers train.py touches (`filter_keys`, `img2mse`, `mse2psnr2`, `init_log`,
-`sub_selete_data`).  Visualisation, PFM/IO, pose-path generators, `homo_warp` and schedulers are out of scope
+`sub_selete_data`), and the depth pictures `visualize_depth` / `visualize_depth_numpy` without cv2 or PIL (a 256 x 3 colour table from
+`utils.colormaps` stands for cv2's colour map).  PFM/IO, pose-path generators, `homo_warp` and schedulers are out of scope
 (SURVEY.md 2.1 row 6).
 
 Random pixel selection (randint / multinomial / numpy shifts) stays host-side torch/numpy logic exactly where the
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import colormaps
 
 img2mse = lambda x, y: torch.mean((x - y) ** 2)                     # noqa: E731
 mse2psnr2 = lambda x: -10. * np.log(x) / np.log(10.)                # noqa: E731
@@ -291,3 +293,63 @@ def build_color_volume(point_samples, pose_ref, imgs, near_far=None, img_feat=No
     feats = ops._FeatGather.apply(None, None, None, None, img_feat, imgs, pose_ref['w2cs'], pose_ref['intrinsics'],
                                   point_samples, None, None, None)
     return feats[..., 24:24 + (12 if img_feat is not None else 4) * V]
+
+
+# ------------------------------------------------------------------------------------------------ depth pictures
+_F32 = np.float32
+_DEVICE_TABLES = {}
+
+
+def _device_table(cmap, device):
+    """The colour table as a device tensor: a device tensor is used where it is, the default Jet is uploaded once per device."""
+    if torch.is_tensor(cmap) and cmap.is_cuda:
+        return ops.colormap_table(cmap, device)
+    if cmap is None:
+        key = str(device)
+        t = _DEVICE_TABLES.get(key)
+        if t is None:
+            t = _DEVICE_TABLES[key] = ops.colormap_table(colormaps.jet_lut(), device)
+        return t
+    return ops.colormap_table(colormaps.as_table(cmap), device)
+
+
+def _depth_index_numpy(x, minmax, positive_min=False):
+    """The float32 arithmetic of utils/utils.py:45-53 / :65-73 on x = nan_to_num(depth): -> (uint8 index map, mi, ma).  numpy leaves the uint8
+    conversion of a NaN or of a value outside 0 .. 255 undefined; here, as in ucnerf_depth_colormap: NaN -> 0, below 0 -> 0, above 255 -> 255."""
+    with np.errstate(all="ignore"):
+        if minmax is None:
+            mi, ma = (np.min(x[x > 0]) if positive_min else np.min(x)), np.max(x)      # np.float32 scalars
+            lo, d = mi, _F32(_F32(ma - mi) + _F32(1e-8))                                 # the Python float stays weak: all in float32
+        else:
+            mi, ma = minmax
+            lo, d = _F32(float(mi)), _F32(float(ma) - float(mi) + 1e-8)                  # Python floats: the denominator in double, rounded once
+        v = _F32(255.0) * ((x - lo) / d)                                                 # two roundings
+        v = np.where(np.isnan(v), _F32(0.0), np.minimum(np.maximum(v, _F32(0.0)), _F32(255.0)))
+    return v.astype(np.uint8), mi, ma                                                    # (in range: truncation toward zero)
+
+
+def visualize_depth(depth, minmax=None, cmap=None):
+    """utils/utils.py:58-77: depth [H,W] -> the colour picture [3,H,W] float32 in [0, 1].  `cmap` is a 256 x 3 uint8 table (default
+    utils.colormaps.jet_lut(), which stands for cv2.COLORMAP_JET and is NOT verified against OpenCV); channel c of the picture is column c of the
+    table -- the reference hands cv2's B, G, R rows to PIL as R, G, B, so with an OpenCV-ordered table channel 0 is OpenCV's blue, as it shows it.
+    A tensor on a ROCm device goes through ucnerf_depth_minmax / ucnerf_depth_colormap and comes back as a device tensor: no host read.  A numpy
+    array or CPU tensor takes the same float32 arithmetic in numpy and comes back as a CPU tensor (what ToTensor returns).  Values are taken as
+    float32.  The one place this is stricter than numpy: the uint8 conversion of NaN / below 0 / above 255 is 0 / 0 / 255 (numpy: undefined)."""
+    if torch.is_tensor(depth) and depth.is_cuda:
+        d = depth.detach().to(torch.float32)
+        return ops.depth_colormap(d, _device_table(cmap, d.device), minmax=minmax, want_index=False)[1]
+    x = np.nan_to_num(np.asarray(depth.detach().numpy() if torch.is_tensor(depth) else depth, dtype=_F32))
+    table = colormaps.as_table(cmap)
+    if x.size == 0:
+        return torch.zeros((3,) + x.shape, dtype=torch.float32)
+    idx, _, _ = _depth_index_numpy(x, minmax)
+    img = table[idx].astype(_F32) / _F32(255.0)                                          # ToTensor: uint8 / 255 in float32
+    return torch.from_numpy(np.ascontiguousarray(np.moveaxis(img, -1, 0)))
+
+
+def visualize_depth_numpy(depth, minmax=None, cmap=None):
+    """utils/utils.py:40-55: numpy depth [H,W] -> (uint8 picture [H,W,3] in the table's column order, [mi, ma]); without `minmax` the range
+    starts at the smallest POSITIVE depth (the background is ignored).  Host-side numpy, as in the reference."""
+    x = np.nan_to_num(np.asarray(depth, dtype=_F32))
+    idx, mi, ma = _depth_index_numpy(x, minmax, positive_min=True)
+    return colormaps.as_table(cmap)[idx], [mi, ma]

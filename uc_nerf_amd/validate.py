@@ -1,0 +1,55 @@
+"""One whole validation image on the device: the body of the reference's validation_step (train.py:249-289) without its host round trips.
+
+The reference renders an image in chunks, pulls every chunk to the host, concatenates, clamps and permutes there, and colours two depth maps
+with cv2 + PIL.  Here a chunk goes from `rendering()` straight into the image planes (ucnerf_image_put: clamp, transpose and the depth range in
+one launch), the depth pictures are one launch each (ucnerf_depth_colormap), and everything returned is a device tensor that
+`utils.evaluation.rgb_evaluation` / `depth_evaluation` take as it is -- a validation image costs the one small read those make.
+Nothing in this module reads the device back.
+"""
+import torch
+
+from . import ops
+from .network.renderer import rendering
+from .utils.utils import _device_table, build_rays_test, visualize_depth
+
+
+def render_validation_image(args, pose_ref, outputs, imgs_input, photo_confidence, H, W, near_fars, render_kwargs, network_fn=None, depth_gt=None,
+                            gt_rgb=None, cmap=None):
+    """train.py:249-289.  The reference's chunk loop -- H W // args.chunk chunks and a partial last one, `build_rays_test` then `rendering` with
+    its arguments (img_feat = outputs["stage3"]["img_feats"], confidence = photo_confidence, **render_kwargs), including rendering's in-place
+    trim of `pose_ref` -- under torch.no_grad().  -> the reference's log dict, every value a device tensor:
+        pred_rgb [3,H,W] clamped to [0, 1], pred_depth [H,W];  with gt_rgb: gt_rgb;  with depth_gt [H,W]: gt_depth, mask = gt_depth > 0;
+    and three more keys: pred_depth_vis [3,H,W] (visualize_depth of pred_depth, its range taken from the cell the chunks were folded into),
+    gt_depth_vis (with depth_gt), uncertainty [H,W] = network_fn.forward_uncertainty(photo_confidence) (network_fn defaults to
+    render_kwargs["network_fn"]).  `cmap`: a 256 x 3 uint8 table, default utils.colormaps.jet_lut()."""
+    H, W = int(H), int(W)
+    net = network_fn if network_fn is not None else render_kwargs["network_fn"]
+    log = {}
+    with torch.no_grad():
+        world_to_ref = pose_ref['w2cs'][0]
+        tgt_to_world, intrinsic = pose_ref['c2ws'][0], pose_ref['intrinsics'][0]
+        dev = tgt_to_world.device
+        render_rgb = torch.empty(3, H, W, device=dev)
+        render_depth = torch.empty(H, W, device=dev)
+        cell = ops.minmax_reset(device=dev)
+        for chunk_idx in range(H * W // args.chunk + int(H * W % args.chunk > 0)):
+            rays_pts, rays_dir, rays_NDC, depth_candidates, rays_o, ndc_parameters = build_rays_test(
+                H, W, tgt_to_world, world_to_ref, intrinsic, near_fars, near_fars[-1], args.N_samples, pad=args.pad, chunk=args.chunk,
+                idx=chunk_idx, outputs=outputs)
+            rgb, depth_pred = rendering(args, pose_ref, rays_pts, rays_NDC, depth_candidates, rays_dir, outputs, imgs_input,
+                                        near_fars=near_fars[0], img_feat=outputs["stage3"]['img_feats'], confidence=photo_confidence,
+                                        ndc_parameters=ndc_parameters, **render_kwargs)
+            ops.image_put(rgb, depth_pred, chunk_idx * args.chunk, render_rgb, render_depth, cell)
+        table = _device_table(cmap, dev)
+        log['pred_depth'] = render_depth
+        log['pred_rgb'] = render_rgb
+        if gt_rgb is not None:
+            log['gt_rgb'] = gt_rgb.to(dev)
+        if depth_gt is not None:
+            depth_gt = depth_gt.to(dev)
+            log['gt_depth'] = depth_gt
+            log['mask'] = depth_gt > 0
+            log['gt_depth_vis'] = visualize_depth(depth_gt, cmap=table)
+        log['pred_depth_vis'] = ops.depth_colormap(render_depth, table, minmax=cell, want_index=False)[1]
+        log['uncertainty'] = net.forward_uncertainty(photo_confidence.reshape(1, -1, 1)).reshape(H, W)
+    return log
