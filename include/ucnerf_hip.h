@@ -1011,6 +1011,14 @@ int ucnerf_render_fused_fwd_if(const ucnerf_render_params* p, const uint32_t* ru
  * Redo it whenever the repacked sources change (once per image in evaluation, once per step in training): ~150 MB of traffic for all five. */
 int64_t ucnerf_gather_repack_floats(const ucnerf_render_params* p);
 int ucnerf_gather_repack(const ucnerf_render_params* p, float* dst, ucnerf_cl_sources* out, void* stream);
+/* The same, for the sources named in `source_mask` only (additive to ABI v6): bits 0..2 the volumes, bit 3 the image features, bit 4 the colours;
+ * ucnerf_gather_repack is this call with UCNERF_REPACK_ALL.  A source whose bit is clear is neither read nor written: its part of `dst` keeps what an
+ * earlier call left there.  The layout of `dst` does not depend on the mask -- `out` receives the entries of the full repack on every call -- and
+ * every source that is written gets the very bytes the full repack writes.  A bit that names a source handed over in place is ignored; a null
+ * reference-layout pointer is an error only for a source that is written.  source_mask == 0: no launch, UCNERF_OK.  For a caller that knows which
+ * sources changed since their copies were made (images stay while volumes and feature maps are replaced: 0x0f instead of all five). */
+#define UCNERF_REPACK_ALL 0x1fu
+int ucnerf_gather_repack_masked(const ucnerf_render_params* p, float* dst, ucnerf_cl_sources* out, uint32_t source_mask, void* stream);
 
 /* Backward of one render pass: d(rgb_map, depth_map) -> d(parameters), d(volumes, img_feat, confidence).
  * fwd.raw and fwd.feats must point at the buffers the forward call filled (keep them); all g_* outputs are

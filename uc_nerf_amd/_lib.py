@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UCNERF_LIB") or os.path.join(_HERE, "libucnerf_hip.so")   # override: A/B builds
 
 ABI_VERSION = 6    # UCNERF_ABI_VERSION of include/ucnerf_hip.h this binding mirrors
+REPACK_ALL = 0x1f  # UCNERF_REPACK_ALL: every source of ucnerf_gather_repack_masked (bits 0..2 volumes, 3 image features, 4 colours)
 
 fp = C.POINTER(C.c_float)
 i32 = C.c_int32
@@ -314,6 +315,7 @@ SYMBOLS = {
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),
     "ucnerf_gather_repack": (C.c_int, [_P, _P, _P, _P]),
+    "ucnerf_gather_repack_masked": (C.c_int, [_P, _P, _P, C.c_uint32, _P]),      # (additive to ABI v6)
     "ucnerf_render_bwd_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_bwd": (C.c_int, [_P, _P]),
 }

@@ -15,11 +15,12 @@
 namespace ucnerf {
 
 // ------------------------------------------------------------------------------------------------ repack
-// One launch for all four sources (blockIdx.y = source; blocks past a source's size exit): the three volumes and the
+// One launch for all the sources it rebuilds (blockIdx.y = row of the table below; blocks past a source's size exit): the three volumes and the
 // image stack are 5-13 us of copying each, so four launches were mostly launch latency.
 struct RepackArgs {
     const float* vol[3]; float4* vol_dst[3]; size_t n_vox[3];       // (a source with a null destination is skipped: it is read in place)
     const float* feat; float4* feat_dst; const float* imgs; float4* col_dst; int V; size_t hw;
+    int rows[5];                                                    // the selected sources, compacted: grid.y entries (0..2 volumes, 3 image features, 4 colours)
 };
 
 // two floats -> one dword of two bf16 (round to nearest even), first value in the low half
@@ -30,11 +31,11 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
 }
 
 // S16: the copies hold bf16 (SURVEY.md 8 configs[4] "bf16 features"): a voxel / feature pixel is 16 bytes, a colour 8 -- half the bytes of every corner
-// blockIdx.y: 0..2 volumes, 3 image features, 4 colours
+// rows[blockIdx.y]: 0..2 volumes, 3 image features, 4 colours
 template <bool S16>
 __global__ void __launch_bounds__(256) repack_sources_kernel(RepackArgs a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int k = blockIdx.y;
+    const int k = a.rows[blockIdx.y];
     if (k < 4) {
         const size_t n_vox = k < 3 ? a.n_vox[k] : a.hw;              // positions per channel plane
         const size_t n_all = k < 3 ? n_vox : (size_t)a.V * a.hw;
@@ -239,7 +240,7 @@ int64_t ucnerf_gather_repack_floats(const ucnerf_render_params* p) {
     return (int64_t)(n[0] + n[1] + n[2] + n[3] + n[4]);
 }
 
-int ucnerf_gather_repack(const ucnerf_render_params* p, float* dst, ucnerf_cl_sources* out, void* stream) {
+int ucnerf_gather_repack_masked(const ucnerf_render_params* p, float* dst, ucnerf_cl_sources* out, uint32_t source_mask, void* stream) {
     UCNERF_REQUIRE(p && out, "gather_repack: null pointer");
     size_t n[5];
     repack_sizes(p, n);
@@ -251,24 +252,43 @@ int ucnerf_gather_repack(const ucnerf_render_params* p, float* dst, ucnerf_cl_so
     memset(&a, 0, sizeof(a));
     ucnerf_cl_sources o = p->cl;
     o.rgb_stride = p->cl.imgs ? p->cl.rgb_stride : 4;
+    // the layout of `dst` and the entries of `out` are those of the full repack whatever the mask says; the mask only decides which rows are written
     float* q = dst;
     size_t n_max = 0;
+    int n_rows = 0;
     for (int k = 0; k < 3; ++k) {
         a.n_vox[k] = (size_t)p->vol_d[k] * p->vol_h[k] * p->vol_w[k];
         if (!n[k]) continue;
-        UCNERF_REQUIRE(p->vol[k], "gather_repack: null volume %d", k);
-        a.vol[k] = p->vol[k]; a.vol_dst[k] = (float4*)q; o.vol[k] = q; q += n[k];
-        if (a.n_vox[k] > n_max) n_max = a.n_vox[k];
+        o.vol[k] = q;
+        if (source_mask >> k & 1) {
+            UCNERF_REQUIRE(p->vol[k], "gather_repack: null volume %d", k);
+            a.vol[k] = p->vol[k]; a.vol_dst[k] = (float4*)q; a.rows[n_rows++] = k;
+            if (a.n_vox[k] > n_max) n_max = a.n_vox[k];
+        }
+        q += n[k];
     }
     a.V = p->cfg.n_src; a.hw = (size_t)p->H * p->W;
-    if (n[3]) { UCNERF_REQUIRE(p->img_feat, "gather_repack: null image features"); a.feat = p->img_feat; a.feat_dst = (float4*)q; o.img_feat = q; q += n[3]; }
-    if (n[4]) { UCNERF_REQUIRE(p->imgs, "gather_repack: null images"); a.imgs = p->imgs; a.col_dst = (float4*)q; o.imgs = q; q += n[4]; }
-    if ((n[3] || n[4]) && a.hw * a.V > n_max) n_max = a.hw * a.V;
+    if (n[3]) {
+        o.img_feat = q;
+        if (source_mask >> 3 & 1) { UCNERF_REQUIRE(p->img_feat, "gather_repack: null image features"); a.feat = p->img_feat; a.feat_dst = (float4*)q; a.rows[n_rows++] = 3; }
+        q += n[3];
+    }
+    if (n[4]) {
+        o.imgs = q;
+        if (source_mask >> 4 & 1) { UCNERF_REQUIRE(p->imgs, "gather_repack: null images"); a.imgs = p->imgs; a.col_dst = (float4*)q; a.rows[n_rows++] = 4; }
+        q += n[4];
+    }
+    if ((a.feat_dst || a.col_dst) && a.hw * a.V > n_max) n_max = a.hw * a.V;
     *out = o;
-    if (!any) return UCNERF_OK;
-    if (p->cl.bf16) hipLaunchKernelGGL(repack_sources_kernel<true>, dim3(cdiv(n_max, 256), 5), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(repack_sources_kernel<false>, dim3(cdiv(n_max, 256), 5), dim3(256), 0, (hipStream_t)stream, a);
+    if (!n_rows || !n_max) return UCNERF_OK;
+    const dim3 grid(cdiv(n_max, 256), n_rows);
+    if (p->cl.bf16) hipLaunchKernelGGL(repack_sources_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(repack_sources_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     return check_launch("gather_repack");
+}
+
+int ucnerf_gather_repack(const ucnerf_render_params* p, float* dst, ucnerf_cl_sources* out, void* stream) {
+    return ucnerf_gather_repack_masked(p, dst, out, UCNERF_REPACK_ALL, stream);
 }
 
 }  // extern "C"

@@ -185,7 +185,7 @@ class FusedSession:
             return old
         self.src = ops.GatherSources(vols, conf, imgs, img_feat, w2cs, intrinsics, cl_bf16=bf16)
         if heavy_ok:
-            self.src._cl, self.src.cl_all = old._cl, old.cl_all
+            self.src.adopt_copies(old)
         self.src_sig, self.src_refs = (hsig, lsig), ([r for _, r in heavy], [r for _, r in light])
         self._src_quick, self._src_keep = quick, (list(vols), imgs, img_feat, conf, w2cs, intrinsics)
         return self.src

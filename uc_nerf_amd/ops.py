@@ -587,6 +587,32 @@ class GatherSources:
         self.cl_inplace.rgb_stride, self.cl_inplace.bf16 = self.rgb_stride, int(self.cl_bf16)
         self.cl_all = self.cl_inplace if self.zero_copy else None
         self._cl = None
+        # What the copies in _cl are copies OF, per source (0..2 volumes, 3 img_feat, 4 imgs): the source tensor's version counter at the moment its
+        # copy was built (None: not built, or built by a launch that was only recorded into a graph).  This object holds the tensors, so their
+        # addresses cannot come back under another tensor while it lives; the counter says whether they were written since.  _cl_gen counts the
+        # allocations of _cl: a RenderPass that took its pointers from an earlier one takes them again (nothing here is keyed on an address).
+        self._cl_versions = [None] * 5
+        self._cl_gen = 0
+
+    def _cl_tensors(self):
+        return self.vols + [self.img_feat, self.imgs]
+
+    def stale_mask(self):
+        """Bit k set: source k is repacked (not read in place) and its channel-last copy is not known to hold the tensor's current values -- the
+        `source_mask` of ucnerf_gather_repack_masked that brings the copies up to date.  Seen: every write that bumps the tensor's version
+        counter (in-place ops, copy_, an optimizer's step).  NOT seen: a write through `.data`, or by another library through the raw pointer --
+        RenderPass.repack_sources(force=True) after those."""
+        m = 0
+        for k, t in enumerate(self._cl_tensors()):
+            if t is not None and not self.inplace[k] and self._cl_versions[k] != t._version:
+                m |= 1 << k
+        return m
+
+    def adopt_copies(self, old):
+        """Takes over the channel-last copies of `old`, a GatherSources of the very same volumes, images and image features (same tensors, same
+        versions: the caller vouches for that) -- with what is known about them.  Sizes that do not match are found by repack_sources, which then
+        starts over."""
+        self._cl, self.cl_all, self._cl_versions, self._cl_gen = old._cl, old.cl_all, list(old._cl_versions), old._cl_gen
 
     def fill(self, p):
         p.V, p.H, p.W = self.V, self.H, self.W
@@ -1748,6 +1774,7 @@ class RenderPass:
         self.src = src
         src.fill(self.p)
         self.use_cl = False
+        self._cl_gen = None                          # (GatherSources._cl_gen of the copies self.p.cl points into)
         self.p.cl = src.cl_inplace                   # (a copy: the in-place sources, if any; the others' entries stay NULL until repack_sources)
         if src.zero_copy:                            # every source IS channel-last: nothing to repack, now or later
             self.use_cl = True
@@ -1761,23 +1788,47 @@ class RenderPass:
         self.p.white_bkgd = int(bool(white_bkgd))
 
     def repack_sources(self, force=True):
-        """(Re)builds the channel-last copies of the sources that are not handed over in place; call whenever those changed.  The copies
-        belong to the sources object: with force=False existing ones (made through any RenderPass bound to them) are reused."""
+        """(Re)builds the channel-last copies of the sources that are not handed over in place.  The copies belong to the sources object (every
+        RenderPass bound to it reads the same ones).
+        force=True: all of them, unconditionally.  force=False: existing ones (made through any RenderPass bound to these sources) are reused as
+        they are, whatever happened to the tensors since.  force="changed": brings them up to date -- only the sources whose tensor was written
+        since its copy was made are rebuilt (GatherSources.stale_mask: by version counter; see there for what that cannot see), all of them when
+        there are no copies yet, none -- no launch -- when nothing changed.  While the stream is being captured into a graph "changed" means True:
+        a replay cannot ask the host what changed, so the graph records the full repack."""
         src = self.src
         if src.zero_copy:                            # (never written: the arrays are the caller's)
             self.p.cl = src.cl_inplace
             self.use_cl = True
             return
+        capturing = torch.cuda.is_current_stream_capturing() if src.device.type == "cuda" else False
+        if (force == "changed" and not capturing and self.use_cl and src._cl is not None and src.cl_all is not None
+                and self._cl_gen == src._cl_gen and not src.stale_mask()):
+            return                                   # (the step's usual case: this pass already reads the copies, and they are current)
         self.p.cl = src.cl_inplace
         n = L.lib().ucnerf_gather_repack_floats(C.addressof(self.p))
         fresh = src._cl is None or src._cl.numel() != n or src.cl_all is None
         if fresh:
             src._cl = torch.empty(n, device=src.device)
             src.cl_all = L.ClSources()
-        if fresh or force:
+            src._cl_versions = [None] * 5
+            src._cl_gen += 1
+        if fresh or capturing and force:
+            mask = L.REPACK_ALL
+        elif force == "changed":
+            mask = src.stale_mask()
+        else:
+            mask = L.REPACK_ALL if force else 0
+        if mask:
+            versions = [None if t is None else t._version for t in src._cl_tensors()]
             with _on(src.device):
-                L.check(L.lib().ucnerf_gather_repack(C.addressof(self.p), _ptr(src._cl), C.addressof(src.cl_all), _stream()), "ucnerf_gather_repack")
+                L.check(L.lib().ucnerf_gather_repack_masked(C.addressof(self.p), _ptr(src._cl), C.addressof(src.cl_all), mask, _stream()),
+                        "ucnerf_gather_repack_masked")
+            if not capturing:                        # (a recorded launch has not run: the copies are what they were)
+                for k in range(5):
+                    if mask >> k & 1 and not src.inplace[k]:
+                        src._cl_versions[k] = versions[k]
         self.p.cl = src.cl_all
+        self._cl_gen = src._cl_gen
         self.use_cl = True
 
     @staticmethod

@@ -1,7 +1,7 @@
 """The 64 coarse + 128 fine hierarchical renderer composed from the library's entry points
 (ray_marcher -> render -> sample_pdf on mid-points with w[1:-1] -> sorted merge -> render).
 
-Library calls per batch (+ the source repack when asked), all on the caller's stream:
+Library calls per batch (+ the source repack for the sources that changed since their channel-last copies were made), all on the caller's stream:
   ray_gen_sample (rays + coarse depths) -> render_fused_fwd (coarse; its compositing launch also runs sample_pdf + merge) -> render_fused_fwd (the
   network on the n_fine NEW depths, evaluation only) -> composite_merged_fwd (compositing over the new rows and the coarse pass's kept rows, read
   in merged order: no merged array).
@@ -79,7 +79,7 @@ class CoarseFineRenderer:
     def _pass_for(self, n_samples):
         """The render pass serving a pass of `n_samples` samples (see fused_min_samples)."""
         if self.pass_small is not None and n_samples < self.fused_min_samples:
-            if self.pass_.use_cl and not self.pass_small.use_cl:
+            if self.pass_.use_cl and (not self.pass_small.use_cl or self.pass_small._cl_gen != self.src._cl_gen):
                 self.pass_small.repack_sources(force=False)      # (the channel-last copies belong to the shared sources object)
             return self.pass_small
         return self.pass_
@@ -104,8 +104,13 @@ class CoarseFineRenderer:
 
     def render(self, xs, ys, perturb=0.0, noise=None, u=None, events=None, repack=True, reuse_coarse=None):
         """xs, ys: pixel coordinates [n] (device, float32).  events: optional [(start, stop), (start, stop)]
-        Event pairs recorded around the coarse and the fine MLP launches.  repack: rebuild the channel-last source
-        copies first (needed whenever volumes / images / features changed since the last call).
+        Event pairs recorded around the coarse and the fine MLP launches.
+        repack: what happens to the channel-last copies of the sources before the step.  True (default): they are brought up to date -- a source
+        (each volume, the image features, the images: on its own) whose tensor was written since its copy was made is copied again, in one launch
+        for all of them; a step on unchanged sources launches nothing (RenderPass.repack_sources(force="changed")).  "Written" is what the tensor's
+        version counter says: in-place ops, copy_, optimizer steps are seen; a write through `.data`, or by another library through the raw
+        pointer, is NOT -- pass repack="force" (all copies rebuilt, unconditionally) after those.  False: the copies are used as they are.
+        While a graph is being captured (capture()) True records the full repack: a replay cannot ask the host what changed.
         reuse_coarse: the fine pass evaluates the network on the n_fine NEW depths only and takes the n_coarse coarse
         depths' outputs from the coarse pass (a sample's output depends on nothing but that sample, so the merged
         rows -- and everything composited from them -- are bit-identical to re-evaluating all n_coarse + n_fine, which is
@@ -116,7 +121,7 @@ class CoarseFineRenderer:
         buffers (coarse["raw"], the merge rank, "disp").  self.fine_route names what was done."""
         sc = self.scene
         if repack:
-            self.pass_.repack_sources()
+            self.pass_.repack_sources(force=True if repack == "force" else "changed")
         # rays and their view-direction feature from one launch; both passes take the feature as an input
         n = int(xs.shape[0])
         explicit = reuse_coarse is not None
@@ -207,7 +212,8 @@ class CoarseFineRenderer:
     def capture(self, n_rays, perturb=0.0, repack=True, reuse_coarse=None):
         """Captures one render of `n_rays` rays into a HIP graph (the launch-bound regime of small
         per-GPU batches).  Returns a callable g(xs, ys, noise=None) -> the same dict as render(); its tensors are owned
-        by the graph and overwritten by the next replay.  Every launch of the step goes to the capturing stream and
+        by the graph and overwritten by the next replay.  repack=True (or "force") records the repack of all the sources: every replay
+        re-reads them.  Every launch of the step goes to the capturing stream and
         the step allocates only through torch's caching allocator, so the capture is a plain stream capture."""
         dev = self.dev
         xs_s, ys_s = torch.zeros(n_rays, device=dev), torch.zeros(n_rays, device=dev)
