@@ -4,7 +4,10 @@
 // ~75 bits, so the reduced argument is good to ~1e-7 absolute for the quadrant counts that occur) followed by the
 // classic degree-7/8 minimax polynomials on [-pi/4, pi/4]: ~25 VALU ops instead of OCML's ~150 (which inlines the
 // Payne-Hanek path branch-free).  Larger arguments (points far outside the frustum) take OCML's sincosf.
-// Measured against torch-CPU's libm on arguments to +-3e5 rad: within 2e-7 absolute (tests: G5).
+// Measured against float64 sin / cos (tests/test_rays_cases_host.py::test_sincos_restatement_is_within_the_header_claim_of_float64, on a
+// float32 restatement that tests/test_hip_ray_edges.py holds the device to bit for bit; the test asserts 2e-7): the fast path is within
+// 9.2e-8 absolute over 1.1 M random |r| <= 65536 and within 9.4e-8 over the 1.5 M floats within 4 ulp of k pi/4, |k| <= 83442 (up to the
+// switch).  sincosf above the switch, on the device: within 6.5e-8 over the 24 388 slow-path slots of the edge case.
 #pragma once
 #include <hip/hip_runtime.h>
 
