@@ -692,8 +692,8 @@ int ucnerf_depth_regress_bwd(const ucnerf_depth_regress_bwd_params* p, void* str
  *     Sizes: h0 <= H, w0 <= W, h <= H, w <= W (any ratio, integer or not).
  *   ROW mode (row given; stage 1): mn = row[0], mx = row[D_in - 1], the same s_d for every pixel; H, W, h0, w0, k, near_far, interval are not read.
  * Exactly one of cur_depth / row is non-NULL.  near and far are read on the device (near_far[0], near_far[1]): no host copy of a device
- * value on this path.  D >= 2.  An output of zero elements (h + 2 pad == 0 or w + 2 pad == 0) is success, nothing launched.  No backward: the
- * reference detaches the depth between stages (grad_method="detach", the only mode it builds).
+ * value on this path.  D >= 2.  An output of zero elements (h + 2 pad == 0 or w + 2 pad == 0) is success, nothing launched.  Backward (map mode, into
+ * cur_depth; near_far and interval get none, row mode has no tensor to differentiate): ucnerf_depth_hypotheses_bwd below.
  * (Declared with a struct tag: the closing line of every typedef above is what tests/test_abi_host.py matches against the v6 struct table of
  *  uc_nerf_amd/_lib.py, which stays as it was; this struct is mirrored in _lib.ADDED_STRUCTS.) */
 struct ucnerf_depth_hypotheses_params {
@@ -710,6 +710,49 @@ struct ucnerf_depth_hypotheses_params {
 };
 typedef struct ucnerf_depth_hypotheses_params ucnerf_depth_hypotheses_params;
 int ucnerf_depth_hypotheses(const ucnerf_depth_hypotheses_params* p, void* stream);
+
+/* The gradients the reference's plain torch expressions carry along depth regression -> depth_values -> depth hypotheses -> previous depth
+ * (CascadeMVSNet with grad_method="undetach", network/mvs_models.py:715-722; both added to ABI v6, nothing above moved).
+ *
+ * ucnerf_depth_regress_bwd_values: depth = sum_d prob_volume[d] * depth_values[d], cropped by `pad`, so
+ *   g_depth_values[d, y + pad, x + pad] = prob_volume[d, y + pad, x + pad] * g_depth[y, x], and 0 on the border of `pad` pixels (the crop drops
+ *   it); the confidence does not depend on depth_values.  Every element of g_depth_values is written.  D, Hp, Wp, pad >= 0, Hp >= 2 pad,
+ *   Wp >= 2 pad, Hp * Wp < 2^31; a volume of zero elements is success, nothing launched; g_depth is read only where the cropped map is not empty.
+ *
+ * ucnerf_depth_hypotheses_bwd: the backward of ucnerf_depth_hypotheses in MAP mode, g_out [D, h + 2 pad, w + 2 pad] -> g_cur_depth [h0, w0],
+ *   OVERWRITTEN (not accumulated).  `fwd` holds the forward's parameters (row must be NULL; out is not read).  Per padded output position
+ *   ("column") G0 = sum_d g_d and G1 = sum_d g_d * d / (D - 1); a border column's sums fold onto the edge column it repeats (a corner edge column
+ *   collects the whole (pad + 1)^2 block).  Inner column (y, x) gives ly[a] * lx[b] * ((G0 - G1) * pass_lo + G1 * pass_hi) to each of its 2 x 2
+ *   full-resolution taps (Y_a, X_b), with pass_lo = (c - half >= near), pass_hi = (c + half <= far), c the forward's own bilinear sample of
+ *   cur_depth there and half = D / 2 * interval_pixel: TIES PASS, as the backward of torch's clamp does.  Each full-resolution pixel hands its
+ *   sum on to its 2 x 2 taps in cur_depth with the up-sampling weights.  Where both taps of an axis are the same pixel (edge clamp, 1-pixel axis)
+ *   both weights count.
+ *   Three launches, every one a GATHER over the destinations whose taps include the pixel a thread owns (a conservative candidate range from the
+ *   scale, membership decided by the forward's own tap rule): no atomics, a fixed summation order, the same bits from every launch.
+ *   `scratch`: ucnerf_depth_hypotheses_bwd_scratch_floats(&fwd) = 2 h w + H W floats (the column sums and the full-resolution gradient,
+ *   327 KB + at most 655 KB at 256 x 320), the caller's allocation on the stream of the call; < 0 on bad sizes.
+ *   Validation as the forward's (negative sizes, D >= 2, the cover conditions, plane < 2^31 and H W < 2^31) comes first; then an empty g_cur_depth
+ *   (h0 == 0 or w0 == 0) is success with nothing launched and no pointer read; then NULL pointers are refused; an empty g_out with a non-empty
+ *   g_cur_depth zero-fills it.
+ * (Both structs are declared with a struct tag and mirrored in _lib.ADDED_STRUCTS.) */
+struct ucnerf_depth_regress_bwd_values_params {
+    int32_t D, Hp, Wp, pad;
+    const float* prob_volume;  /* [D,Hp,Wp] the forward's output */
+    const float* g_depth;      /* [Hp - 2 pad, Wp - 2 pad] */
+    float* g_depth_values;     /* [D,Hp,Wp] out */
+};
+typedef struct ucnerf_depth_regress_bwd_values_params ucnerf_depth_regress_bwd_values_params;
+int ucnerf_depth_regress_bwd_values(const ucnerf_depth_regress_bwd_values_params* p, void* stream);
+
+struct ucnerf_depth_hypotheses_bwd_params {
+    struct ucnerf_depth_hypotheses_params fwd;  /* map mode: cur_depth, near_far (and interval) as the forward had them; row NULL; out not read */
+    const float* g_out;        /* [D, h + 2 pad, w + 2 pad] */
+    float* scratch;            /* ucnerf_depth_hypotheses_bwd_scratch_floats(&fwd) floats */
+    float* g_cur_depth;        /* [h0, w0] out, overwritten */
+};
+typedef struct ucnerf_depth_hypotheses_bwd_params ucnerf_depth_hypotheses_bwd_params;
+int64_t ucnerf_depth_hypotheses_bwd_scratch_floats(const ucnerf_depth_hypotheses_params* fwd);
+int ucnerf_depth_hypotheses_bwd(const ucnerf_depth_hypotheses_bwd_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * e1   evaluation metrics on the device -- utils/evaluation.py:8-74 (compute_errors, depth_evaluation) and :76-101 (rgb_evaluation: PSNR and

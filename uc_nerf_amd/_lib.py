@@ -151,6 +151,14 @@ class DepthHypothesesParams(C.Structure):
                 ("cur_depth", vp), ("row", vp), ("near_far", vp), ("interval", vp), ("out", vp)]
 
 
+class DepthRegressBwdValuesParams(C.Structure):
+    _fields_ = [("D", i32), ("Hp", i32), ("Wp", i32), ("pad", i32), ("prob_volume", vp), ("g_depth", vp), ("g_depth_values", vp)]
+
+
+class DepthHypothesesBwdParams(C.Structure):
+    _fields_ = [("fwd", DepthHypothesesParams), ("g_out", vp), ("scratch", vp), ("g_cur_depth", vp)]
+
+
 class BuildRaysTrainParams(C.Structure):
     _fields_ = [("S", i32), ("H", i32), ("W", i32), ("P", i32), ("ps", i32), ("n_uniform", i32), ("n_coord", i32), ("coord_stride", i32),
                 ("dv_d", i32 * 3), ("dv_h", i32 * 3), ("dv_w", i32 * 3), ("img_stride_c", C.c_int64), ("img_stride_h", C.c_int64),
@@ -231,7 +239,9 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_image_eval_params": ImageEvalParams, "ucnerf_composite_merged_bwd_params": CompositeMergedBwdParams,
                  "ucnerf_cas_loss_params": CasLossParams, "ucnerf_cas_loss_bwd_params": CasLossBwdParams,
                  "ucnerf_image_put_params": ImagePutParams, "ucnerf_depth_minmax_params": DepthMinmaxParams,
-                 "ucnerf_depth_colormap_params": DepthColormapParams}
+                 "ucnerf_depth_colormap_params": DepthColormapParams,
+                 "ucnerf_depth_regress_bwd_values_params": DepthRegressBwdValuesParams,
+                 "ucnerf_depth_hypotheses_bwd_params": DepthHypothesesBwdParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -296,6 +306,10 @@ SYMBOLS = {
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress_bwd": (C.c_int, [_P, _P]),
     "ucnerf_depth_hypotheses": (C.c_int, [_P, _P]),
+    # the gradient chain depth regression -> depth_values -> hypotheses -> previous depth (additive to ABI v6)
+    "ucnerf_depth_regress_bwd_values": (C.c_int, [_P, _P]),
+    "ucnerf_depth_hypotheses_bwd_scratch_floats": (C.c_int64, [_P]),
+    "ucnerf_depth_hypotheses_bwd": (C.c_int, [_P, _P]),
     # the evaluation metrics (additive to ABI v6)
     "ucnerf_eval_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_depth_eval": (C.c_int, [_P, _P]),

@@ -269,6 +269,26 @@ __global__ void __launch_bounds__(DR_PIX * DR_DL) depth_regress_bwd_kernel(ucner
     }
 }
 
+// ---- the other branch of the depth regression's backward: depth = sum_d p_d * depth_values_d, cropped by pad, so
+// g_depth_values[d] = p_d * g_depth inside the crop and 0 on the border.  One thread per pixel of the padded plane and chunk of DRV_DEPTHS
+// depths (blockIdx.y), consecutive threads = consecutive pixels: a wave reads and writes 256 contiguous bytes of one depth plane.
+constexpr int DRV_BLOCK = 256, DRV_DEPTHS = 8;
+
+__global__ void __launch_bounds__(DRV_BLOCK) depth_regress_bwd_values_kernel(ucnerf_depth_regress_bwd_values_params p) {
+    const unsigned plane = (unsigned)p.Hp * (unsigned)p.Wp;                  // (host checks plane < 2^31)
+    const unsigned t = blockIdx.x * DRV_BLOCK + threadIdx.x;
+    if (t >= plane) return;
+    const int yy = (int)(t / (unsigned)p.Wp) - p.pad, xx = (int)(t % (unsigned)p.Wp) - p.pad;
+    const int H = p.Hp - 2 * p.pad, W = p.Wp - 2 * p.pad;
+    const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
+    const float g = inside ? p.g_depth[(size_t)yy * W + xx] : 0.f;
+    const int d_begin = blockIdx.y * DRV_DEPTHS, d_end = min(d_begin + DRV_DEPTHS, p.D);
+    for (int d = d_begin; d < d_end; ++d) {
+        const size_t at = (size_t)d * plane + t;
+        p.g_depth_values[at] = inside ? p.prob_volume[at] * g : 0.f;
+    }
+}
+
 }  // namespace ucnerf
 
 using namespace ucnerf;
@@ -318,6 +338,20 @@ int ucnerf_depth_regress_bwd(const ucnerf_depth_regress_bwd_params* bp, void* st
     const long long plane = (long long)p->Hp * p->Wp;
     hipLaunchKernelGGL(depth_regress_bwd_kernel, dim3(cdiv(plane, DR_PIX)), dim3(DR_PIX * DR_DL), 0, (hipStream_t)stream, *bp);
     return check_launch("depth_regress_bwd");
+}
+
+int ucnerf_depth_regress_bwd_values(const ucnerf_depth_regress_bwd_values_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "depth_regress_bwd_values: null params");
+    UCNERF_REQUIRE(p->D >= 0 && p->Hp >= 0 && p->Wp >= 0 && p->pad >= 0, "depth_regress_bwd_values: negative size D=%d Hp=%d Wp=%d pad=%d", p->D, p->Hp, p->Wp, p->pad);
+    UCNERF_REQUIRE(p->D <= 65535 * DRV_DEPTHS, "depth_regress_bwd_values: D = %d above %d", p->D, 65535 * DRV_DEPTHS);
+    UCNERF_REQUIRE(p->Hp >= 2ll * p->pad && p->Wp >= 2ll * p->pad, "depth_regress_bwd_values: Hp=%d Wp=%d do not hold a border of pad=%d", p->Hp, p->Wp, p->pad);
+    const long long plane = (long long)p->Hp * p->Wp;
+    UCNERF_REQUIRE(plane < (1ll << 31), "depth_regress_bwd_values: plane of %lld pixels (32-bit pixel index)", plane);
+    if (plane == 0 || p->D == 0) return UCNERF_OK;                           // an empty volume: success, nothing launched, no pointer read
+    const bool crop_empty = p->Hp == 2 * p->pad || p->Wp == 2 * p->pad;      // all border: zeros, g_depth has no element to read
+    UCNERF_REQUIRE(p->prob_volume && p->g_depth_values && (crop_empty || p->g_depth), "depth_regress_bwd_values: null pointer");
+    hipLaunchKernelGGL(depth_regress_bwd_values_kernel, dim3(cdiv(plane, DRV_BLOCK), cdiv(p->D, DRV_DEPTHS)), dim3(DRV_BLOCK), 0, (hipStream_t)stream, *p);
+    return check_launch("depth_regress_bwd_values");
 }
 
 }  // extern "C"

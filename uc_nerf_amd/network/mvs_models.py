@@ -8,7 +8,11 @@ stay the caller's modules (MIOpen territory).
 
 The cost volume and the regression have backward kernels behind `torch.autograd.Function`s, so the feature network
 trains through the variance volume and the regularisation network through depth and photometric confidence, as in the
-reference.  The hypothesis volume carries no gradient: the reference detaches the depth between stages.
+reference.  The chain depth regression -> depth_values -> depth hypotheses -> previous depth has backward kernels too
+(`ucnerf_depth_regress_bwd_values`, `ucnerf_depth_hypotheses_bwd`): with `grad_method="detach"` (the reference's
+default) the depth is detached between stages and the hypothesis volume carries no gradient; with `"undetach"` it
+stays in the graph, as the reference's other branch keeps it, and a loss on a later stage's depth reaches the earlier
+stages' regularisers.
 `features` may be a list of [1,C,H,W] maps (as the reference passes) or a stacked tensor.
 """
 import torch
@@ -62,7 +66,8 @@ def _batch_one(t, what):
 
 
 def get_cur_depth_range_samples(cur_depth, ndepth, depth_inteval_pixel, shape, max_depth=192.0, min_depth=0.0):
-    """mvs_models.py:536-551.  cur_depth [1,H,W] -> [1,D,H,W]: `ucnerf_depth_hypotheses` with the output at the map's own resolution."""
+    """mvs_models.py:536-551.  cur_depth [1,H,W] -> [1,D,H,W]: `ucnerf_depth_hypotheses` with the output at the map's own resolution.
+    Differentiable with respect to cur_depth, as the reference's torch expressions are (the bounds and the interval get no gradient)."""
     if tuple(cur_depth.shape) != tuple(shape):
         raise AssertionError("cur_depth:{}, input shape:{}".format(cur_depth.shape, shape))
     c = _batch_one(cur_depth, "get_cur_depth_range_samples")
@@ -87,14 +92,19 @@ class CascadeMVSNet(nn.Module):
     (volume feature, logits [1,1,D,h,w]); an nn.ModuleList / sequence with one per stage, or ONE module with share_cr) are handed in --
     they are registered under the reference's attribute names, so a reference checkpoint's `feature.*` / `cost_regularization.*` keys load.
     Per stage: `ucnerf_depth_hypotheses` (one launch, replicate border included) -> `DepthNet` (cost volume, the caller's regulariser,
-    depth regression)."""
+    depth regression).  grad_method "detach": the previous stage's depth is detached before the next stage's hypotheses are built; "undetach"
+    (the other branch of :716-719): it is not, and the hypotheses, the regressed depth and so the earlier stages carry its gradient.  The reference
+    takes ANY other string for that branch; here a value that is neither of the two is refused, so that a misspelt "detach" does not silently
+    change what trains."""
+
+    GRAD_METHODS = ("detach", "undetach")
 
     def __init__(self, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
                  arch_mode="fpn", cr_base_chs=[8, 8, 8], *, feature=None, cost_regularization=None):
         super().__init__()
-        if grad_method != "detach":
-            raise NotImplementedError("uc_nerf_amd CascadeMVSNet: grad_method=%r -- only \"detach\" (the reference's default, the only mode it "
-                                      "builds): the hypothesis kernel has no backward" % (grad_method,))
+        if grad_method not in self.GRAD_METHODS:
+            raise NotImplementedError("uc_nerf_amd CascadeMVSNet: grad_method=%r -- \"detach\" (the reference's default: the depth is detached between "
+                                      "stages) or \"undetach\" (it stays in the graph)" % (grad_method,))
         missing = [n for n, m in (("feature", feature), ("cost_regularization", cost_regularization)) if m is None]
         if missing:
             raise ValueError("uc_nerf_amd CascadeMVSNet: the CNNs are the caller's modules -- pass %s=... (the reference's FeatureNet / "
@@ -142,8 +152,9 @@ class CascadeMVSNet(nn.Module):
             if depth is None:
                 depth_value = ops.depth_hypotheses(D, (H // scale, W // scale), row=near_far, pad=stage_pad)
             else:
+                cur_depth = depth.detach() if self.grad_method == "detach" else depth                # :716-719
                 # depth_inteval_pixel = ratio * (far - near) / 48: the reference divides by the literal 48 (:694,698), not by ndepths[0]
-                depth_value = ops.depth_hypotheses(D, (H // scale, W // scale), cur_depth=depth.detach()[0], near_far=near_far,
+                depth_value = ops.depth_hypotheses(D, (H // scale, W // scale), cur_depth=cur_depth[0], near_far=near_far,
                                                    k=self.depth_interals_ratio[stage_idx] / 48.0, full_hw=(H, W), pad=stage_pad)
             cr = self.cost_regularization if self.share_cr else self.cost_regularization[stage_idx]
             outputs_stage = self.DepthNet(features_stage, affine_mat[:, stage_idx], affine_mat_inv[:, stage_idx], depth_values=depth_value.unsqueeze(0),

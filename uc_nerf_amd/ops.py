@@ -1411,24 +1411,93 @@ class _DepthRegressFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _g_prob, g_depth, g_conf):
         prob, depth_values = ctx.saved_tensors
-        bp = L.DepthRegressBwdParams()
-        bp.fwd = _depth_regress_params(prob, None, depth_values, ctx.pad)
-        bp.fwd.prob_volume = _ptr(prob)
         g_depth = _f32(g_depth, "g_depth") if g_depth is not None else None
         g_conf = _f32(g_conf, "g_confidence") if g_conf is not None else None
-        g_x = torch.empty_like(prob)
-        bp.g_depth, bp.g_confidence, bp.g_prob_pre = _ptr(g_depth), _ptr(g_conf), _ptr(g_x)
-        _launch("ucnerf_depth_regress_bwd", bp, prob.device)
-        return g_x, None, (g_x if ctx.has_init else None), None
+        g_x = g_dv = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            bp = L.DepthRegressBwdParams()
+            bp.fwd = _depth_regress_params(prob, None, depth_values, ctx.pad)
+            bp.fwd.prob_volume = _ptr(prob)
+            g_x = torch.empty_like(prob)
+            bp.g_depth, bp.g_confidence, bp.g_prob_pre = _ptr(g_depth), _ptr(g_conf), _ptr(g_x)
+            _launch("ucnerf_depth_regress_bwd", bp, prob.device)
+        if ctx.needs_input_grad[1]:                       # depth = sum_d p_d * depth_values_d: the hypotheses' own gradient
+            g_dv = _depth_regress_bwd_values(prob, g_depth, ctx.pad)
+        return g_x, g_dv, (g_x if ctx.has_init else None), None
+
+
+def _depth_regress_bwd_values(prob, g_depth, pad):
+    """g_depth_values [D,Hp,Wp] = prob * g_depth inside the crop, 0 on the border of `pad` pixels (`ucnerf_depth_regress_bwd_values`)."""
+    D, Hp, Wp = prob.shape
+    g_dv = torch.empty_like(prob)
+    if g_depth is None:
+        return g_dv.zero_()
+    if tuple(g_depth.shape) != (Hp - 2 * pad, Wp - 2 * pad):
+        raise RuntimeError("uc_nerf_amd.depth_regress: g_depth %s for a volume %s cropped by %d" % (tuple(g_depth.shape), tuple(prob.shape), pad))
+    p = L.DepthRegressBwdValuesParams()
+    p.D, p.Hp, p.Wp, p.pad = D, Hp, Wp, int(pad)
+    p.prob_volume, p.g_depth, p.g_depth_values = _ptr(prob), _ptr(g_depth), _ptr(g_dv)
+    _launch("ucnerf_depth_regress_bwd_values", p, prob.device)
+    return g_dv
 
 
 def depth_regress(prob_pre, depth_values, prob_init=None, pad=0):
     """softmax over depth, expected depth and 4-tap photometric confidence (network/mvs_models.py:629-646).
     prob_pre, depth_values (and prob_init) [D,Hp,Wp] -> (prob_volume [D,Hp,Wp] (detached, as in the reference), depth
-    [H,W], confidence [H,W]); depth and confidence are differentiable with respect to the logits."""
+    [H,W], confidence [H,W]); depth and confidence are differentiable with respect to the logits, and depth with respect to depth_values
+    (depth = sum_d p_d * depth_values_d, as the reference's torch expression is; the confidence does not depend on them)."""
     prob_pre, depth_values = _f32(prob_pre, "prob_pre"), _f32(depth_values, "depth_values")
     prob_init = _f32(prob_init, "prob_init") if prob_init is not None else None
-    return _DepthRegressFn.apply(prob_pre, depth_values.detach(), prob_init, int(pad))
+    return _DepthRegressFn.apply(prob_pre, depth_values, prob_init, int(pad))
+
+
+def _depth_hypotheses_map_params(cur_depth, near_far, interval, sizes):
+    p = L.DepthHypothesesParams()
+    p.D, p.h, p.w, p.pad, p.H, p.W, p.k = sizes
+    p.h0, p.w0 = cur_depth.shape
+    p.cur_depth, p.near_far, p.interval = _ptr(cur_depth), _ptr(near_far), _ptr(interval)
+    return p
+
+
+class _DepthHypothesesFn(torch.autograd.Function):
+    """Map mode of `depth_hypotheses` under autograd: differentiable in cur_depth; near_far and interval get no gradient."""
+
+    @staticmethod
+    def forward(ctx, cur_depth, near_far, interval, sizes):
+        D, h, w, pad = sizes[:4]
+        p = _depth_hypotheses_map_params(cur_depth, near_far, interval, sizes)
+        out = torch.empty(max(D, 0), max(h + 2 * pad, 0), max(w + 2 * pad, 0), device=cur_depth.device)
+        p.out = _ptr(out)
+        _launch("ucnerf_depth_hypotheses", p, cur_depth.device)
+        ctx.save_for_backward(cur_depth, near_far, *(() if interval is None else (interval,)))
+        ctx.sizes = sizes
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        cur_depth, near_far = ctx.saved_tensors[:2]
+        interval = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        return depth_hypotheses_bwd(_f32(g_out, "g_out"), cur_depth, near_far, interval, ctx.sizes), None, None, None
+
+
+def depth_hypotheses_bwd(g_out, cur_depth, near_far, interval, sizes):
+    """`ucnerf_depth_hypotheses_bwd`: g_out [D, h + 2 pad, w + 2 pad] -> g_cur_depth [h0,w0] for the map-mode call with sizes =
+    (D, h, w, pad, H, W, k).  Three gather launches through a scratch of 2 h w + H W floats from torch's allocator (on the current stream, so
+    a capture stays a plain stream capture); no atomics, the same bits from every call.  What autograd runs behind `depth_hypotheses`."""
+    dev = cur_depth.device
+    D, h, w, pad = sizes[:4]
+    if tuple(g_out.shape) != (max(D, 0), max(h + 2 * pad, 0), max(w + 2 * pad, 0)):
+        raise RuntimeError("uc_nerf_amd.depth_hypotheses_bwd: g_out %s for sizes %s" % (tuple(g_out.shape), tuple(sizes)))
+    bp = L.DepthHypothesesBwdParams()
+    bp.fwd = _depth_hypotheses_map_params(cur_depth, near_far, interval, sizes)
+    n = L.lib().ucnerf_depth_hypotheses_bwd_scratch_floats(C.addressof(bp.fwd))
+    if n < 0:
+        raise RuntimeError("uc_nerf_amd.depth_hypotheses_bwd: " + L.lib().ucnerf_last_error().decode())
+    scratch = torch.empty(n, device=dev)
+    g_cur = torch.empty_like(cur_depth)
+    bp.g_out, bp.scratch, bp.g_cur_depth = _ptr(g_out), _ptr(scratch), _ptr(g_cur)
+    _launch("ucnerf_depth_hypotheses_bwd", bp, dev)
+    return g_cur
 
 
 def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=0.0, full_hw=None, pad=0, interval=None):
@@ -1436,7 +1505,8 @@ def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=
     -> depth_values [ndepth, h + 2 pad, w + 2 pad], (h, w) = out_hw, the border of `pad` pixels repeating the edge (DepthNet's replicate pad).
     Map mode: cur_depth [h0,w0] = the previous stage's depth, near_far a DEVICE tensor (near, far), interval_pixel = k * (far - near) -- or
     k * interval for a one-element device tensor `interval` --, full_hw the resolution the reference up-samples to before it interpolates back down (default: out_hw).  Row mode: row [D_in], the band
-    row[0] .. row[-1] for every pixel.  No autograd: the inputs are taken detached, as the reference hands them over."""
+    row[0] .. row[-1] for every pixel.  Differentiable with respect to cur_depth (map mode, when it requires grad and grad mode is on:
+    `ucnerf_depth_hypotheses_bwd`, ties of the two clamps pass as torch's clamp does); near_far, interval and row are taken detached."""
     if (cur_depth is None) == (row is None):
         raise RuntimeError("uc_nerf_amd.depth_hypotheses: exactly one of cur_depth (map mode) and row (row mode)")
     h, w = int(out_hw[0]), int(out_hw[1])
@@ -1444,6 +1514,7 @@ def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=
     p = L.DepthHypothesesParams()
     p.D, p.h, p.w, p.pad, p.H, p.W, p.k = int(ndepth), h, w, int(pad), H, W, float(k)
     if cur_depth is not None:
+        cur_in = cur_depth
         cur_depth = _f32(cur_depth.detach(), "cur_depth")
         if cur_depth.dim() != 2 or near_far is None:
             raise RuntimeError("uc_nerf_amd.depth_hypotheses: map mode takes cur_depth [h0,w0] and near_far")
@@ -1457,6 +1528,8 @@ def depth_hypotheses(ndepth, out_hw, cur_depth=None, row=None, near_far=None, k=
             if interval.numel() != 1 or interval.device != cur_depth.device:
                 raise RuntimeError("uc_nerf_amd.depth_hypotheses: interval must hold one value on cur_depth's device")
             p.interval = _ptr(interval)
+        if cur_in.requires_grad and torch.is_grad_enabled():
+            return _DepthHypothesesFn.apply(_f32(cur_in, "cur_depth"), near_far, interval, (p.D, h, w, p.pad, H, W, p.k))
         dev = cur_depth.device
     else:
         row = _f32(row.detach(), "row")

@@ -130,7 +130,7 @@ def _stage_ranges(outputs, pix):
     (stage 1 at 1/4 resolution, stage 2 at 1/2): utils/utils.py:659-683."""
     cols = []
     for key, div in (("stage1", 4), ("stage2", 2), ("stage3", 1)):
-        dv = outputs[key]['depth_values']
+        dv = outputs[key]['depth_values'].detach()         # (read as data: a cascade that keeps its depth in the graph hands over volumes that carry one)
         r = torch.div(pix[0], div, rounding_mode='trunc').long()
         c = torch.div(pix[1], div, rounding_mode='trunc').long()
         cols += [dv[0, 0, r, c], dv[0, -1, r, c]]
