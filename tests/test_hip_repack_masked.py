@@ -255,7 +255,56 @@ def test_no_stale_copy_across_reallocation():
     c.render(**rays)
     c.src._cl, c.src.cl_all = None, None                          # (the buffer is dropped under both passes)
     _assert_same(c.render(**rays), _renderer(_clone(big), flat, fused_min_rounds=4).render(**rays))
-    assert c.pass_small._cl_gen == c.src._cl_gen == c.pass_._cl_gen
+    lo = c.src._cl.data_ptr()
+    for rp in (c.pass_, c.pass_small):                            # both passes are bound to the new buffer: every repacked source, inside it
+        for k in range(5):
+            bound, want = ((x.vol[k] if k < 3 else x.img_feat if k == 3 else x.imgs) for x in (rp.p.cl, c.src.cl_all))
+            assert c.src.inplace[k] or (lo <= bound < lo + 4 * c.src._cl.numel() and bound == want), k
+
+
+def _ops_pass(scene, flat):
+    """(GatherSources of the scene's tensors, a way to bind an f32 ops.RenderPass to sources)"""
+    from uc_nerf_amd import ops
+
+    def sources(sc):
+        return ops.GatherSources(sc["vols"], sc["confidence"], sc["imgs"], sc["img_feat"], sc["w2cs"][1:], sc["intrinsics"][1:])
+
+    def bind(src):
+        pw = ops.PackedWeights.get(src.V, 0, torch.device(DEV), "f32")
+        return ops.RenderPass(src, pw, pw.pack(flat), scene["c2w"][:3, 3], scene["w2cs"][0], scene["intrinsics"][0], scene["w2cs"][0],
+                              scene["near"], scene["far"])
+    return sources, bind
+
+
+def test_second_pass_follows_a_reallocation_without_being_told():
+    """Two ops.RenderPass objects on one GatherSources, no renderer around them.  The buffer of copies is dropped and pass `a` builds it again
+    (from sources written in the meantime); pass `b`, called with no repack call of any kind, reads the new buffer: its outputs are those of a
+    pass on fresh sources of the changed tensors, bit for bit.  (A pass that kept the pointers it was given once would render the old values.)
+    Ends the process, with every thread's stack, should it take longer than 120 s."""
+    import faulthandler
+    faulthandler.dump_traceback_later(120, exit=True)
+    try:
+        scene, flat, rays = _clone(_scene(3)), _flat(3), _rays()
+        sources, bind = _ops_pass(scene, flat)
+        rays_d, _, z = _renderer(scene, flat, precision="f32").sampler(rays["xs"], rays["ys"], rays["perturb"], rays["noise"])
+        src = sources(scene)
+        a, b = bind(src), bind(src)
+        a.repack_sources()
+        b.repack_sources(force=False)
+        before = a(rays_d, z)
+        _assert_same(b(rays_d, z), before)
+        _write(scene, (0, 3))
+        dropped = src._cl                                         # (kept alive here: the new buffer is another allocation, the old one stays valid memory)
+        src._cl, src.cl_all = None, None
+        a.repack_sources("changed")
+        assert src._cl.data_ptr() != dropped.data_ptr()
+        got = b(rays_d, z)
+        fresh = bind(sources(_clone(scene)))
+        fresh.repack_sources()
+        _assert_same(got, fresh(rays_d, z))
+        assert not torch.equal(got["rgb"], before["rgb"])         # (the write shows in the render: the old copies would not have passed)
+    finally:
+        faulthandler.cancel_dump_traceback_later()
 
 
 # ------------------------------------------------------------------------------------------------ 4: .data

@@ -577,7 +577,7 @@ class GatherSources:
         self.device = dev
         self.full = self.mask == (0b1111 | (((1 << self.V) - 1) << 4))
         self.zero_copy = all(self.inplace)          # every source is read in place: nothing to repack, now or later
-        # ucnerf_cl_sources of the in-place sources alone, and of all five once RenderPass.repack_sources has completed them (shared by every
+        # ucnerf_cl_sources of the in-place sources alone, and of all five once repack() has completed them (shared by every
         # RenderPass bound to these sources); _cl: the buffer the repacked ones live in
         self.cl_inplace = L.ClSources()
         for k in range(3):
@@ -590,9 +590,10 @@ class GatherSources:
         # What the copies in _cl are copies OF, per source (0..2 volumes, 3 img_feat, 4 imgs): the source tensor's version counter at the moment its
         # copy was built (None: not built, or built by a launch that was only recorded into a graph).  This object holds the tensors, so their
         # addresses cannot come back under another tensor while it lives; the counter says whether they were written since.  _cl_gen counts the
-        # allocations of _cl: a RenderPass that took its pointers from an earlier one takes them again (nothing here is keyed on an address).
+        # allocations of _cl (nothing here is keyed on an address); a RenderPass takes cl_all anew at every call and needs no counter.
         self._cl_versions = [None] * 5
         self._cl_gen = 0
+        self._repack_p, self._cl_floats = None, None        # repack()'s own parameter struct and the floats _cl must have, made at its first call
 
     def _cl_tensors(self):
         return self.vols + [self.img_feat, self.imgs]
@@ -610,9 +611,43 @@ class GatherSources:
 
     def adopt_copies(self, old):
         """Takes over the channel-last copies of `old`, a GatherSources of the very same volumes, images and image features (same tensors, same
-        versions: the caller vouches for that) -- with what is known about them.  Sizes that do not match are found by repack_sources, which then
+        versions: the caller vouches for that) -- with what is known about them.  Sizes that do not match are found by repack(), which then
         starts over."""
         self._cl, self.cl_all, self._cl_versions, self._cl_gen = old._cl, old.cl_all, list(old._cl_versions), old._cl_gen
+
+    def repack(self, force=True):
+        """(Re)builds the channel-last copies of the sources that are not handed over in place, in _cl; cl_all then names all five.
+        force=True: all of them.  force=False: existing ones are reused as they are, whatever happened to the tensors since.  force="changed":
+        only the sources whose tensor was written since its copy was made (stale_mask: by version counter; see there for what that cannot see);
+        no launch and no library call when nothing changed.  All are built when there are no copies yet or the buffer does not fit these sources
+        (adopt_copies).  While the stream is being captured "changed" means True: a replay cannot ask the host what changed.
+        Of the parameter struct the library reads H, W, vol_d / vol_h / vol_w, vol, img_feat, imgs (fill()), cfg.n_src (V) and cl (cl_inplace): nothing of a pass."""
+        if self.zero_copy:                           # (never written: the arrays are the caller's)
+            return
+        if self._repack_p is None:
+            p = self._repack_p = L.RenderParams()
+            self.fill(p)
+            p.cfg.n_src, p.cl = self.V, self.cl_inplace
+            self._cl_floats = L.lib().ucnerf_gather_repack_floats(C.addressof(p))
+        capturing = torch.cuda.is_current_stream_capturing() if self.device.type == "cuda" else False
+        fresh = self._cl is None or self._cl.numel() != self._cl_floats or self.cl_all is None
+        if fresh:
+            self._cl = torch.empty(self._cl_floats, device=self.device)
+            self.cl_all = L.ClSources()
+            self._cl_versions = [None] * 5
+            self._cl_gen += 1
+        if fresh or (force and (capturing or force != "changed")):
+            mask = L.REPACK_ALL
+        else:
+            mask = self.stale_mask() if force else 0         # (0: the step's usual case)
+        if mask:
+            with _on(self.device):
+                L.check(L.lib().ucnerf_gather_repack_masked(C.addressof(self._repack_p), _ptr(self._cl), C.addressof(self.cl_all), mask, _stream()),
+                        "ucnerf_gather_repack_masked")
+            if not capturing:                        # (a recorded launch has not run: the copies are what they were)
+                for k, t in enumerate(self._cl_tensors()):
+                    if mask >> k & 1 and not self.inplace[k]:
+                        self._cl_versions[k] = None if t is None else t._version
 
     def fill(self, p):
         p.V, p.H, p.W = self.V, self.H, self.W
@@ -683,6 +718,15 @@ def feat_gather_bwd(src, pts, ndc1, ndc2, ndc3, g_feats, need=(True, True, True,
     return gv[0], gv[1], gv[2], gc, gi
 
 
+def _bind_gather_grads(bp, gv, gi, cl):
+    """Hands a gather backward its gradient arrays (None: not wanted): the volumes' gv[0..2] and the image features' gi, in g_cl where cl[k] says
+    the array is channel-last (k = 3: gi), in g_vol / g_img_feat otherwise.  Returns whether any is channel-major: those go through the scratch buffer."""
+    for k in range(3):
+        bp.g_vol[k], bp.g_cl.vol[k] = (None, _ptr(gv[k])) if cl[k] else (_ptr(gv[k]), None)
+    bp.g_img_feat, bp.g_cl.img_feat = (None, _ptr(gi)) if cl[3] else (_ptr(gi), None)
+    return any(g is not None and not c for g, c in zip((*gv, gi), cl))
+
+
 def _feat_gather_bwd_into(src, pts, ndc1, ndc2, ndc3, g_feats, grads, route):
     """One call of ucnerf_feat_gather_bwd ACCUMULATING into `grads` (what feat_gather_bwd returned for the same sources and route)."""
     pts, ndc1, ndc2, ndc3, g_feats = _opt(pts), _opt(ndc1), _opt(ndc2), _opt(ndc3), _f32(g_feats)
@@ -694,13 +738,8 @@ def _feat_gather_bwd_into(src, pts, ndc1, ndc2, ndc3, g_feats, grads, route):
     bp.fwd.pts, bp.fwd.ndc1, bp.fwd.ndc2, bp.fwd.ndc3 = _ptr(pts), _ptr(ndc1), _ptr(ndc2), _ptr(ndc3)
     bp.g_feats = _ptr(g_feats)
     gv, gc, gi = grads[:3], grads[3], grads[4]
-    for k in range(3):
-        bp.g_vol[k] = None if cl_vol else _ptr(gv[k])
-        bp.g_cl.vol[k] = _ptr(gv[k]) if cl_vol else None
     bp.g_conf = _ptr(gc)
-    bp.g_img_feat = None if cl_feat else _ptr(gi)
-    bp.g_cl.img_feat = _ptr(gi) if cl_feat else None
-    via_scratch = (not cl_vol and any(g is not None for g in gv)) or (not cl_feat and gi is not None)
+    via_scratch = _bind_gather_grads(bp, gv, gi, (cl_vol, cl_vol, cl_vol, cl_feat))
     bp.scratch = _ptr(_gather_scratch(src, bp.fwd, lead.device)) if (route == "scratch" or (via_scratch and route != "direct")) else None
     _launch("ucnerf_feat_gather_bwd", bp, lead.device)
 
@@ -1846,11 +1885,16 @@ class RenderPass:
         """Binds (other) gather sources; the fast gather is used once repack_sources() has run for them."""
         self.src = src
         src.fill(self.p)
-        self.use_cl = False
-        self._cl_gen = None                          # (GatherSources._cl_gen of the copies self.p.cl points into)
-        self.p.cl = src.cl_inplace                   # (a copy: the in-place sources, if any; the others' entries stay NULL until repack_sources)
-        if src.zero_copy:                            # every source IS channel-last: nothing to repack, now or later
-            self.use_cl = True
+        self.use_cl = src.zero_copy                  # (every source IS channel-last: nothing to repack, now or later)
+        self._bind_cl(self.p)
+
+    def _bind_cl(self, p):
+        """Points a call's parameters at the channel-last sources as they are NOW: all five where this pass reads the copies (built first,
+        should the buffer have been dropped under it), the in-place ones alone -- the others' entries NULL -- otherwise."""
+        src = self.src
+        if self.use_cl and src.cl_all is None:
+            src.repack(False)
+        p.cl = src.cl_all if self.use_cl else src.cl_inplace
 
     def set_weights(self, pw, wstream):
         self.pw, self.wstream = pw, wstream
@@ -1861,48 +1905,11 @@ class RenderPass:
         self.p.white_bkgd = int(bool(white_bkgd))
 
     def repack_sources(self, force=True):
-        """(Re)builds the channel-last copies of the sources that are not handed over in place.  The copies belong to the sources object (every
-        RenderPass bound to it reads the same ones).
-        force=True: all of them, unconditionally.  force=False: existing ones (made through any RenderPass bound to these sources) are reused as
-        they are, whatever happened to the tensors since.  force="changed": brings them up to date -- only the sources whose tensor was written
-        since its copy was made are rebuilt (GatherSources.stale_mask: by version counter; see there for what that cannot see), all of them when
-        there are no copies yet, none -- no launch -- when nothing changed.  While the stream is being captured into a graph "changed" means True:
-        a replay cannot ask the host what changed, so the graph records the full repack."""
-        src = self.src
-        if src.zero_copy:                            # (never written: the arrays are the caller's)
-            self.p.cl = src.cl_inplace
-            self.use_cl = True
-            return
-        capturing = torch.cuda.is_current_stream_capturing() if src.device.type == "cuda" else False
-        if (force == "changed" and not capturing and self.use_cl and src._cl is not None and src.cl_all is not None
-                and self._cl_gen == src._cl_gen and not src.stale_mask()):
-            return                                   # (the step's usual case: this pass already reads the copies, and they are current)
-        self.p.cl = src.cl_inplace
-        n = L.lib().ucnerf_gather_repack_floats(C.addressof(self.p))
-        fresh = src._cl is None or src._cl.numel() != n or src.cl_all is None
-        if fresh:
-            src._cl = torch.empty(n, device=src.device)
-            src.cl_all = L.ClSources()
-            src._cl_versions = [None] * 5
-            src._cl_gen += 1
-        if fresh or capturing and force:
-            mask = L.REPACK_ALL
-        elif force == "changed":
-            mask = src.stale_mask()
-        else:
-            mask = L.REPACK_ALL if force else 0
-        if mask:
-            versions = [None if t is None else t._version for t in src._cl_tensors()]
-            with _on(src.device):
-                L.check(L.lib().ucnerf_gather_repack_masked(C.addressof(self.p), _ptr(src._cl), C.addressof(src.cl_all), mask, _stream()),
-                        "ucnerf_gather_repack_masked")
-            if not capturing:                        # (a recorded launch has not run: the copies are what they were)
-                for k in range(5):
-                    if mask >> k & 1 and not src.inplace[k]:
-                        src._cl_versions[k] = versions[k]
-        self.p.cl = src.cl_all
-        self._cl_gen = src._cl_gen
+        """Brings the channel-last copies of the sources up to date and makes this pass read them.  The copies belong to the sources object (every
+        RenderPass bound to it reads the same ones): GatherSources.repack says what force=True / False / "changed" rebuild."""
+        self.src.repack(force)
         self.use_cl = True
+        self._bind_cl(self.p)
 
     @staticmethod
     def _coords(p, coords, m):
@@ -1942,6 +1949,7 @@ class RenderPass:
         dev = z.device
         p = self.p
         p.n, p.S = n, S
+        self._bind_cl(p)
         need = L.lib().ucnerf_render_workspace_floats(n, S, self.src.V)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=dev)
@@ -2038,6 +2046,7 @@ class RenderPass:
         C.memmove(C.addressof(bp.fwd), C.addressof(self.p), C.sizeof(L.RenderParams))
         p = bp.fwd
         p.n, p.S = n, S
+        self._bind_cl(p)
         near_far = _f32(near_far) if near_far is not None else None
         p.rays_d, p.z, p.near_far = _ptr(rays_d), _ptr(z), _ptr(near_far)
         p.raw, p.feats = _ptr(kept["raw"]), _ptr(kept["feats"])
@@ -2093,15 +2102,8 @@ class RenderPass:
             gi = segs[5].view(shapes[5])
         g_depth = _f32(g_depth) if g_depth is not None else None
         bp.g_rgb, bp.g_depth, bp.flat_params, bp.g_flat, bp.workspace = _ptr(g_rgb), _ptr(g_depth), _ptr(flat), _ptr(g_flat), _ptr(ws)
-        for k in range(3):
-            bp.g_vol[k] = None if inp[k] else _ptr(gv[k])
-            bp.g_cl.vol[k] = _ptr(segs[1 + k]) if inp[k] else None
         bp.g_conf = _ptr(gc)
-        bp.g_img_feat = None if inp[3] else _ptr(gi)
-        bp.g_cl.img_feat = _ptr(segs[5]) if inp[3] else None
-        via_scratch = any(gv[k] is not None and not inp[k] for k in range(3)) or (gi is not None and not inp[3])
-        bp.gather_scratch = None
-        if via_scratch:
+        if _bind_gather_grads(bp, gv, gi, inp[:4]):
             gfwd = L.FeatGatherParams()
             src.fill(gfwd)
             bp.gather_scratch = _ptr(_gather_scratch(src, gfwd, dev))

@@ -79,7 +79,7 @@ class CoarseFineRenderer:
     def _pass_for(self, n_samples):
         """The render pass serving a pass of `n_samples` samples (see fused_min_samples)."""
         if self.pass_small is not None and n_samples < self.fused_min_samples:
-            if self.pass_.use_cl and (not self.pass_small.use_cl or self.pass_small._cl_gen != self.src._cl_gen):
+            if self.pass_.use_cl and not self.pass_small.use_cl:
                 self.pass_small.repack_sources(force=False)      # (the channel-last copies belong to the shared sources object)
             return self.pass_small
         return self.pass_
