@@ -1086,6 +1086,43 @@ typedef struct {
 int64_t ucnerf_render_bwd_workspace_floats(int32_t n, int32_t S, int32_t V);
 int ucnerf_render_fused_bwd(const ucnerf_render_bwd_params* p, void* stream);
 
+/* Gradient fold of the compositing's extra maps (added to ABI v6; nothing above moved): lets a loss on var, disp or the composited uncertainty
+ * wu = sum_i w_i u_i (ucnerf_composite_params.var / disp_map / wu) reach the network through the backward kernels there are.  All three maps are
+ * functions of weights, depth and acc, whose gradients ucnerf_composite_bwd / ucnerf_composite_merged_bwd accept; this launch adds their
+ * chain-rule terms to the upstream gradients of those three, and the existing backward then runs unchanged on the results.  Per ray, S samples:
+ *   g_weights_out[i] = g_weights[i] + g_var * (2 * (w_i - mean(w)) / (S - 1)) + g_wu * u_i        (var: unbiased, of torch.var_mean)
+ *   g_depth_out      = g_depth + g_disp * (-(disp^2 / acc))                                      (disp = 1 / (depth / acc))
+ *   g_acc_out        = g_acc   + g_disp * ((disp^2 / acc) * (depth / acc))
+ *   g_u[i]           = g_wu * w_i
+ * in fp32, each operation rounded on its own, terms added in the order written; a NULL upstream gradient is zero.  The disp terms are zero at
+ * a ray whose depth / acc is <= 1e-10 (the clamp of 1 / max(1e-10, depth / acc) is active) or not finite.  At depth / acc == 1e-10 exactly
+ * torch.maximum hands half of the gradient to each side; this kernel hands none -- a tie of measure zero.
+ * One 64-lane wave per ray, lane split of ucnerf_composite_fwd (ceil(S/64) -> 1, 2, 3, 4, 8, 16 samples per lane): mean(w) is the forward's
+ * acc / S, bit for bit.  Every element of every output is written exactly once -- no atomics, no zero fill; a second call into the same buffers
+ * gives the same bits.  The merged route needs nothing else: weights, u and the upstream gradients are in merged order already.
+ * 1 <= S <= 1024.  weights, depth, acc, g_depth_out, g_acc_out and g_weights_out are required; u, g_u and every upstream gradient may be NULL.
+ * UCNERF_EINVAL: g_var with S < 2, g_wu without u, an output that overlaps an input or another output, a negative count.  n == 0: success.
+ * (Declared with a struct tag: mirrored in _lib.ADDED_STRUCTS.) */
+struct ucnerf_composite_fold_params {
+    int32_t n, S;
+    const float* weights;      /* [n,S] the forward's outputs ... */
+    const float* depth;        /* [n] */
+    const float* acc;          /* [n] */
+    const float* u;            /* [n,S] the forward's per-sample uncertainty, or NULL */
+    const float* g_var;        /* [n] or NULL: upstream gradients of the extra maps ... */
+    const float* g_disp;       /* [n] or NULL */
+    const float* g_wu;         /* [n] or NULL (needs u) */
+    const float* g_depth;      /* [n] or NULL: ... and of the maps the backward kernels take */
+    const float* g_acc;        /* [n] or NULL */
+    const float* g_weights;    /* [n,S] or NULL */
+    float* g_depth_out;        /* [n] */
+    float* g_acc_out;          /* [n] */
+    float* g_weights_out;      /* [n,S] */
+    float* g_u;                /* [n,S] or NULL: gradient of u (zeros without g_wu) */
+};
+typedef struct ucnerf_composite_fold_params ucnerf_composite_fold_params;
+int ucnerf_composite_fold_grads(const ucnerf_composite_fold_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

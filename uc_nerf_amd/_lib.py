@@ -128,6 +128,11 @@ class CompositeMergedBwdParams(C.Structure):
                 ("g_depth", vp), ("g_acc", vp), ("g_weights", vp), ("g_raw_a", vp), ("g_raw_b", vp)]
 
 
+class CompositeFoldParams(C.Structure):
+    _fields_ = [("n", i32), ("S", i32), ("weights", vp), ("depth", vp), ("acc", vp), ("u", vp), ("g_var", vp), ("g_disp", vp), ("g_wu", vp),
+                ("g_depth", vp), ("g_acc", vp), ("g_weights", vp), ("g_depth_out", vp), ("g_acc_out", vp), ("g_weights_out", vp), ("g_u", vp)]
+
+
 class CostVolumeParams(C.Structure):
     _fields_ = [("V", i32), ("C", i32), ("H", i32), ("W", i32), ("D", i32), ("pad", i32), ("feats", vp), ("proj", vp),
                 ("depth_values", vp), ("variance", vp), ("count", vp)]
@@ -241,7 +246,8 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_image_put_params": ImagePutParams, "ucnerf_depth_minmax_params": DepthMinmaxParams,
                  "ucnerf_depth_colormap_params": DepthColormapParams,
                  "ucnerf_depth_regress_bwd_values_params": DepthRegressBwdValuesParams,
-                 "ucnerf_depth_hypotheses_bwd_params": DepthHypothesesBwdParams}
+                 "ucnerf_depth_hypotheses_bwd_params": DepthHypothesesBwdParams,
+                 "ucnerf_composite_fold_params": CompositeFoldParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -301,6 +307,8 @@ SYMBOLS = {
     "ucnerf_merge_rows": (C.c_int, [_P, _P]),
     "ucnerf_composite_merged_fwd": (C.c_int, [_P, _P]),
     "ucnerf_composite_merged_bwd": (C.c_int, [_P, _P]),
+    # the gradient fold of var / disp / composited uncertainty (additive to ABI v6)
+    "ucnerf_composite_fold_grads": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume": (C.c_int, [_P, _P]),
     "ucnerf_depth_regress": (C.c_int, [_P, _P]),
     "ucnerf_cost_volume_bwd": (C.c_int, [_P, _P]),

@@ -443,6 +443,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_cas_loss_params); SZ(ucnerf_cas_loss_bwd_params);
     SZ(ucnerf_image_put_params); SZ(ucnerf_depth_minmax_params); SZ(ucnerf_depth_colormap_params);
     SZ(ucnerf_depth_regress_bwd_values_params); SZ(ucnerf_depth_hypotheses_bwd_params);
+    SZ(ucnerf_composite_fold_params);
 #undef SZ
     return -1;
 }

@@ -65,6 +65,13 @@ def raw2outputs(raw, z_vals, dists, white_bkgd=False, net_type='v2'):
     return rgb, disp, acc, weights, depth, weights, var
 
 
+def raw2outputs_maps(raw, z_vals, dists, white_bkgd=False, net_type='v2'):
+    """raw2outputs with every map differentiable, as the reference's torch version is: the same 7-tuple from the same forward launch, with
+    disp_map and var carrying gradient to `raw` (ops.composite_maps: one gradient-fold launch in front of the compositing backward)."""
+    rgb, depth, acc, weights, disp, var = ops.composite_maps(raw[..., :4], z_vals, white_bkgd)
+    return rgb, disp, acc, weights, depth, weights, var
+
+
 def gen_dir_feature(w2c_ref, rays_dir):
     """network/renderer.py:163-174: rays_dir @ R_ref^T."""
     return rays_dir @ w2c_ref[:3, :3].t()

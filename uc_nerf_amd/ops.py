@@ -1369,6 +1369,122 @@ def composite_merged(raw_a, raw_b, rank, z, white_bkgd=False):
     return _CompositeMerged.apply(raw_a, raw_b, rank, z, bool(white_bkgd))
 
 
+def composite_fold_grads(weights, depth, acc, u=None, g_var=None, g_disp=None, g_wu=None, g_depth=None, g_acc=None, g_weights=None, want_g_u=None,
+                         out=None):
+    """(g_depth', g_acc', g_weights', g_u): the upstream gradients of the compositing's extra maps -- g_var [n], g_disp [n], g_wu [n] (of
+    sum_i w_i u_i), each optional -- folded into those of depth, acc and weights (each optional: None = zero), ready for composite_bwd /
+    composite_merged_bwd; g_u [n,S] = g_wu * weights is the gradient of u (None unless want_g_u; default: whenever u is given).
+    weights [n,S], depth [n], acc [n]: the forward's outputs (merged order on the merged route); u [n,S]: its per-sample uncertainty.
+    out: (g_depth', g_acc', g_weights', g_u or None) buffers to write into -- every element is written, whatever they held."""
+    weights, depth, acc = _f32(weights, "weights"), _f32(depth, "depth"), _f32(acc, "acc")
+    if weights.dim() != 2:
+        raise RuntimeError("uc_nerf_amd.composite_fold_grads: weights must be [n,S]")
+    n, S = weights.shape
+    dev = weights.device
+    u = _f32(u, "u") if u is not None else None
+    named = dict(depth=(depth, n), acc=(acc, n), u=(u, n * S))
+    ups = dict(g_var=(g_var, n), g_disp=(g_disp, n), g_wu=(g_wu, n), g_depth=(g_depth, n), g_acc=(g_acc, n), g_weights=(g_weights, n * S))
+    for name, (g, numel) in ups.items():
+        named[name] = (_f32(g, name) if g is not None else None, numel)
+    for name, (t, numel) in named.items():
+        if t is not None and (t.numel() != numel or t.device != dev):
+            raise RuntimeError("uc_nerf_amd.composite_fold_grads: %s has %d elements on %s, expected %d on %s" % (name, t.numel(), t.device, numel, dev))
+    if want_g_u is None:
+        want_g_u = u is not None
+    if out is None:
+        out = (torch.empty(n, device=dev), torch.empty(n, device=dev), torch.empty(n, S, device=dev), torch.empty(n, S, device=dev) if want_g_u else None)
+    o_depth, o_acc, o_w, o_u = out
+    for t, numel, name in ((o_depth, n, "g_depth'"), (o_acc, n, "g_acc'"), (o_w, n * S, "g_weights'"), (o_u, n * S, "g_u")):
+        if t is None and name == "g_u":
+            continue
+        if t is None or t.dtype != torch.float32 or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("uc_nerf_amd.composite_fold_grads: out must be contiguous float32 (g_depth' [n], g_acc' [n], g_weights' [n,S], g_u [n,S] or "
+                               "None) on the device; %s is not" % name)
+    p = L.CompositeFoldParams()
+    p.n, p.S = n, S
+    p.weights, p.depth, p.acc, p.u = _ptr(weights), _ptr(depth), _ptr(acc), _ptr(u)
+    p.g_var, p.g_disp, p.g_wu = (_ptr(named[k][0]) for k in ("g_var", "g_disp", "g_wu"))
+    p.g_depth, p.g_acc, p.g_weights = (_ptr(named[k][0]) for k in ("g_depth", "g_acc", "g_weights"))
+    p.g_depth_out, p.g_acc_out, p.g_weights_out, p.g_u = _ptr(o_depth), _ptr(o_acc), _ptr(o_w), _ptr(o_u)
+    _launch("ucnerf_composite_fold_grads", p, dev)
+    return o_depth, o_acc, o_w, o_u
+
+
+def _maps_outputs(ctx, out):
+    """The output tuple of the *_maps functions from a forward's dict: var is differentiable where it exists (S >= 2; zeros without history
+    otherwise, as composite() returns them), wu is there when u was given."""
+    var = out.get("var")
+    if var is None:
+        var = torch.zeros_like(out["acc"])
+        ctx.mark_non_differentiable(var)
+    res = (out["rgb"], out["depth"], out["acc"], out["weights"], out["disp"], var)
+    return res + (out["wu"],) if "wu" in out else res
+
+
+def _maps_fold(ctx, u, weights, depth, acc, g_depth, g_acc, g_weights, g_disp, g_var, g_wu, u_arg):
+    """(g_depth, g_acc, g_weights, g_u) for the existing backward launch: the fold launch when a gradient of an extra map arrived, the
+    upstream gradients as they are otherwise."""
+    if g_var is None and g_disp is None and g_wu is None:
+        return g_depth, g_acc, g_weights, None
+    return composite_fold_grads(weights, depth, acc, u, g_var, g_disp, g_wu, g_depth, g_acc, g_weights,
+                                want_g_u=u is not None and g_wu is not None and ctx.needs_input_grad[u_arg])
+
+
+class _CompositeMaps(torch.autograd.Function):
+    """_Composite with every map differentiable: var, disp and wu hand their gradients to composite_fold_grads, composite_bwd does the rest."""
+
+    @staticmethod
+    def forward(ctx, raw, z, white_bkgd, u):
+        out = composite_fwd(raw, z, 0, white_bkgd, u=u)
+        ctx.save_for_backward(raw, z, u, out["weights"], out["depth"], out["acc"])
+        ctx.white_bkgd = white_bkgd
+        ctx.set_materialize_grads(False)
+        return _maps_outputs(ctx, out)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_acc, g_weights, g_disp, g_var, g_wu=None):
+        raw, z, u, weights, depth, acc = ctx.saved_tensors
+        g_depth, g_acc, g_weights, g_u = _maps_fold(ctx, u, weights, depth, acc, g_depth, g_acc, g_weights, g_disp, g_var, g_wu, 3)
+        g_raw = composite_bwd(raw, z, g_rgb, g_depth, g_acc, g_weights, ctx.white_bkgd) if ctx.needs_input_grad[0] else None
+        return g_raw, None, None, g_u
+
+
+def composite_maps(raw, z, white_bkgd=False, u=None):
+    """(rgb, depth, acc, weights, disp, var[, wu]) of composite(raw, z, white_bkgd) -- the same forward launch -- with EVERY map differentiable
+    w.r.t. raw: a loss on var (unbiased variance of the weights), on disp or on wu = sum_i w_i u_i (returned when the per-sample uncertainty
+    u [n,S] is given; u receives its gradient too) trains the network.  Backward: one composite_fold_grads launch, then composite_bwd; without
+    a gradient on var, disp or wu the fold is skipped and the gradients are composite()'s, bit for bit.  var needs S >= 2 (S = 1: zeros without
+    history, as composite() returns them).  disp has no gradient at a ray where the clamp of 1 / max(1e-10, depth / acc) is active."""
+    return _CompositeMaps.apply(raw, z, bool(white_bkgd), u)
+
+
+class _CompositeMergedMaps(torch.autograd.Function):
+    """_CompositeMerged with every map differentiable; the fold sees weights, u and gradients in merged order and never raw or rank."""
+
+    @staticmethod
+    def forward(ctx, raw_a, raw_b, rank, z, white_bkgd, u):
+        out = composite_merged_fwd(raw_a, raw_b, rank, z, white_bkgd, u=u)
+        ctx.save_for_backward(raw_a, raw_b, rank, z, u, out["weights"], out["depth"], out["acc"])
+        ctx.white_bkgd = white_bkgd
+        ctx.set_materialize_grads(False)
+        return _maps_outputs(ctx, out)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_acc, g_weights, g_disp, g_var, g_wu=None):
+        raw_a, raw_b, rank, z, u, weights, depth, acc = ctx.saved_tensors
+        g_depth, g_acc, g_weights, g_u = _maps_fold(ctx, u, weights, depth, acc, g_depth, g_acc, g_weights, g_disp, g_var, g_wu, 5)
+        g_a = g_b = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g_a, g_b = composite_merged_bwd(raw_a, raw_b, rank, z, g_rgb, g_depth, g_acc, g_weights, ctx.white_bkgd)
+        return g_a, g_b, None, None, None, g_u
+
+
+def composite_merged_maps(raw_a, raw_b, rank, z, white_bkgd=False, u=None):
+    """composite_maps(merge_rows(raw_a, raw_b, rank), z, white_bkgd, u) with no merged array: composite_merged's forward launch, and in the
+    backward one composite_fold_grads launch followed by composite_merged_bwd, bit for bit.  u [n,na+nb] and every map are in merged order."""
+    return _CompositeMergedMaps.apply(raw_a, raw_b, rank, z, bool(white_bkgd), u)
+
+
 # ------------------------------------------------------------------------------------------------ f2
 def _cost_volume_params(feats, proj, depth_values, pad):
     V, Cc, H, W = feats.shape

@@ -182,7 +182,7 @@ class CoarseFineRenderer:
                                 ndc["stage1"], ndc["stage2"], ndc["stage3"])
         return ops.mlp(flat_params, feats, ndc["ndc"], angle, self.pw, S, wstream).view(n, S, 4)
 
-    def render_train(self, xs, ys, flat_params, perturb=0.0, noise=None, u=None):
+    def render_train(self, xs, ys, flat_params, perturb=0.0, noise=None, u=None, maps=False):
         """render(reuse_coarse=True) with autograd history: the same dict, name for name (rgb, depth, acc, disp, weights, var, coarse{rgb, depth,
         weights, raw, samples, z_sorted, merge_rank}, z_coarse, z_fine, z_samples, rays_d; disp and var carry no gradient), differentiable back to `flat_params` and to whichever of the scene's volumes, image features and confidence
         have requires_grad.  xs, ys, perturb, noise, u: as in render().
@@ -190,6 +190,11 @@ class CoarseFineRenderer:
         depths (ops.sample_pdf: no gradient, as in the reference) -> gather + MLP at the NEW depths only -> ops.composite_merged over the new rows
         and the coarse rows.  The coarse rows receive gradient twice -- from the coarse compositing and, as raw_b, from the fine one -- and
         autograd sums the two.  The network runs on a stream packed from `flat_params` here (the renderer's own stream is not touched).
+        maps=True: both compositing steps go through ops.composite_maps / ops.composite_merged_maps instead -- the same forward launches, the
+        same values -- so that `disp` and `var` (and coarse["disp"], coarse["var"], returned in addition) carry gradient: a loss on the
+        weights' variance or on disparity trains the network (one extra launch per compositing step in the backward, and only when such a
+        gradient arrives).  The composited uncertainty wu is not among them: the training forward gathers features, not the per-sample u,
+        as a tensor; ops.composite_maps(raw, z, u=...) takes a loss on it at the ops level.
         Exact-f32 precision only."""
         if self.pw.guarded:
             raise RuntimeError("uc_nerf_amd.CoarseFineRenderer.render_train: the 'fp16_guarded' operand mode is an inference mode -- a launch that "
@@ -200,11 +205,17 @@ class CoarseFineRenderer:
         rays_d, angle, z_c = self.sampler(xs, ys, perturb, noise)
         wstream = self.pw.pack(flat_params.detach())
         raw_c = self._eval_train(flat_params, wstream, rays_d, angle, z_c)
-        rgb_c, depth_c, acc_c, w_c, _, _ = ops.composite(raw_c, z_c, self.white_bkgd)
+        if maps:
+            rgb_c, depth_c, acc_c, w_c, disp_c, var_c = ops.composite_maps(raw_c, z_c, self.white_bkgd)
+        else:
+            rgb_c, depth_c, acc_c, w_c, _, _ = ops.composite(raw_c, z_c, self.white_bkgd)
         hs = ops.sample_pdf(None, w_c.detach(), self.u_det if u is None else u, z_merge=z_c, want_inds=False, from_coarse=True, want_rank=True)
         raw_f = self._eval_train(flat_params, wstream, rays_d, angle, hs["samples"])
-        rgb, depth, acc, weights, disp, var = ops.composite_merged(raw_f, raw_c, hs["merge_rank"], hs["z_sorted"], self.white_bkgd)      # cat(samples, z_coarse) order
+        fine = ops.composite_merged_maps if maps else ops.composite_merged
+        rgb, depth, acc, weights, disp, var = fine(raw_f, raw_c, hs["merge_rank"], hs["z_sorted"], self.white_bkgd)      # cat(samples, z_coarse) order
         coarse = dict(rgb=rgb_c, depth=depth_c, weights=w_c, raw=raw_c, samples=hs["samples"], z_sorted=hs["z_sorted"], merge_rank=hs["merge_rank"])
+        if maps:
+            coarse.update(disp=disp_c, var=var_c)
         return dict(rgb=rgb, depth=depth, acc=acc, disp=disp, weights=weights, var=var, z_coarse=z_c, z_fine=hs["z_sorted"], z_samples=hs["samples"],
                     coarse=coarse, rays_d=rays_d)
 
