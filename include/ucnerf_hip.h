@@ -461,7 +461,25 @@ int ucnerf_mlp_pack_tensors_if(const ucnerf_mlp_config* cfg, int32_t n_tensors, 
  * saved_valid), then walks the layers backwards (bwd_mode).  Produces d(feats) and ACCUMULATES the parameter gradients
  * into g_flat, a vector laid out exactly like the flat parameter vector (zero it first).  The three parameter
  * sets the reference never uses (pts_bias_confidence_1, feature_linear_1, confi_linear) get no contribution.
- * Positions and view directions receive no gradient (the reference path is non-differentiable there). */
+ * Positions and view directions receive no gradient (the reference path is non-differentiable there).
+ *
+ * READABLE EXTENT.  bwd_mode 0 forms every parameter gradient in one launch that fetches its fp32 row operands in 16-byte pieces: four columns,
+ * starting at a column that is a multiple of four, from rows that need only be 4-byte aligned.  A piece that reaches past the operand's last
+ * column is fetched whole and the lanes outside the operand are replaced by zero bits before use (selected, not multiplied: whatever is read
+ * there, a NaN pattern included, reaches no result), but the bytes must be READABLE:
+ *     fwd.encoded = 1:  the 63 encoded point columns are read as 16 pieces, the 27 direction columns as 7 -- the last piece of a row ends ONE
+ *         float behind it.  Inside a [m, 63+F+27] matrix that float is the next column or the next row; behind the last row of `dirs` (the
+ *         end of that matrix) and behind the last row of a separate `pts` buffer it lies outside the rows: 4 readable bytes are required
+ *         behind row m-1 of `pts` and of `dirs` (the torch wrapper copies x into a buffer four floats longer).
+ *     fwd.encoded = 0:  pts / dirs are encoded into the workspace first (rows padded to 64 / 32 floats there): nothing is read behind them,
+ *         and pts_stride / dirs_stride must be 0 or 3.
+ *     feats, row-major: the pieces cover columns [0, 24+4V) and [24+4V, 24+12V), both whole pieces: nothing is read behind column F-1, whatever
+ *         feat_stride.  feats, tile layout: whole tiles are read, the padding rows of the last tile included (they belong to the layout:
+ *         ceil(m/32)*32*F floats); their values reach no result.
+ *     g_raw, flat_params, wstream: read exactly.  The workspace is read only where the call (or ucnerf_mlp_fwd_train) wrote it: it may hold
+ *         anything on entry, apart from the activations under saved_valid = 1.
+ * bwd_mode 1 reads single elements of every operand: no bytes outside the rows described here.  Neither mode writes outside g_feats' F columns per
+ * row, g_flat's param_count floats and the workspace's ucnerf_mlp_bwd_workspace_floats() floats. */
 typedef struct {
     ucnerf_mlp_params fwd;     /* forward arguments (feats row-major [m,F], or tiled with bwd_mode 0); raw is not written */
     const float* g_raw;        /* [m,4] upstream gradient */
@@ -469,9 +487,11 @@ typedef struct {
     float* g_feats;            /* [m,F] out, rows g_feat_stride floats apart (every one of the F columns written) */
     int32_t g_feat_stride;     /* 0 = F */
     float* g_flat;             /* [param_count] accumulated */
-    float* workspace;          /* scratch, ucnerf_mlp_bwd_workspace_floats() floats, 16-byte aligned (kept activations, gradient sets, and --
-                                  bwd_mode 0 -- the weight-gradient launch's 16 chunk counters, which the call zeroes itself: one workspace per
-                                  call in flight) */
+    float* workspace;          /* scratch, ucnerf_mlp_bwd_workspace_floats() floats, 16-byte aligned: kept activations, gradient sets, and the
+                                  state of the two merges, which the call zeroes itself -- bwd_mode 0: the weight-gradient launch's 16 chunk
+                                  counters; bwd_mode 1: the head kernel's arrival counter, behind its 256 rows of 1032 block sums (about 264 k
+                                  floats of the workspace whatever m is).  ONE WORKSPACE PER CALL IN FLIGHT, in either mode: two calls that
+                                  share one corrupt each other's merge */
     int32_t saved_valid;       /* 1: `workspace` already holds the activations of THIS forward, written by
                                   ucnerf_mlp_fwd_train with the same arguments -- the backward then skips its own forward */
     int32_t bwd_mode;          /* 0: register-resident gradient chain (ONE kernel walks the network backwards per 32-sample tile, data

@@ -348,8 +348,11 @@ __global__ void __launch_bounds__(1024) gemm_tn_kernel(TnArgs a) {
 // Output stage (models.py:177-178 backwards) + both 4-wide heads, data AND weight gradients.  32 lanes per sample
 // (4 features each), sixteen samples per block pass, persistent blocks (one per CU): every lane keeps the 4 x 4 products of its
 // features with the head gradients in registers across its samples, the sample slots of a block are summed
-// through LDS at the end and go to the flat gradient with one atomic per weight and block.  (As separate
-// weight-gradient GEMMs these four 1-to-3-row products cost a full pass over the activations each.)
+// through LDS at the end and written to the block's row of `partial`; the block that finishes last adds the rows, in block order,
+// and hands each weight ONE atomic per launch.  The head gradients therefore do not depend on the order the blocks finish in, and
+// a g_flat that holds c on entry holds fl(c + g) afterwards -- with one atomic per weight and BLOCK, (c + p1) + p2 took the place
+// of c + (p1 + p2) wherever two blocks met.  (As separate weight-gradient GEMMs these four 1-to-3-row products cost a full pass
+// over the activations each.)
 struct HeadArgs {
     int m, F;
     const float* raw;     // [m,4] forward output
@@ -367,9 +370,16 @@ struct HeadArgs {
     float* g_vc;          // [m,128] gradient at the pre-relu output of views/view_confi linears
     float* g_feats; int ldgf;       // writes column F-1 (confidence)
     float *gw_crgb, *gw_a1, *gw_rgb, *gw_a, *gb_crgb, *gb_a1, *gb_rgb, *gb_a;     // parameter gradients (accumulated)
+    float* partial;       // [gridDim.x][HEAD_VALUES] block sums (workspace)
+    unsigned* done;       // blocks that have written their row; zeroed before the launch
 };
 
 constexpr int HEAD_SLOTS = 16;                           // samples per block pass (32 lanes each)
+constexpr int HEAD_VALUES = 1024 + 8;                    // block sums: 32 lanes x 32 weight products, 8 bias sums
+// rows of `partial` the workspace holds.  A design limit, not a property of the device: the workspace size is a function of (cfg, m) alone
+// (ucnerf_mlp_bwd_workspace_floats takes no device), so the grid is min(blocks needed, CUs, this) -- on a device with more than 256 CUs
+// the head kernel runs 256 persistent blocks, each walking more samples
+constexpr int HEAD_MAX_BLOCKS = 256;
 __global__ void __launch_bounds__(32 * HEAD_SLOTS) head_bwd_kernel(HeadArgs a) {
     __shared__ float red[HEAD_SLOTS][32][33];            // [sample slot][lane][value] (+1: conflict-free column sums)
     __shared__ float redb[HEAD_SLOTS][8];
@@ -458,7 +468,7 @@ __global__ void __launch_bounds__(32 * HEAD_SLOTS) head_bwd_kernel(HeadArgs a) {
         reinterpret_cast<f32x4*>(a.g_vc + (size_t)s * 128)[c] = g;
     }
 
-    // block sums over the eight sample slots, then one atomic per weight
+    // block sums over the sample slots -> this block's row of `partial`
 #pragma unroll
     for (int o = 0; o < 4; ++o)
 #pragma unroll
@@ -468,26 +478,53 @@ __global__ void __launch_bounds__(32 * HEAD_SLOTS) head_bwd_kernel(HeadArgs a) {
         for (int o = 0; o < 8; ++o) redb[slot][o] = bsum[o];
     }
     __syncthreads();
+    // (agent-scope stores and loads: the rows are written and read by different blocks, possibly behind different L2s)
+    float* mine = a.partial + (size_t)blockIdx.x * HEAD_VALUES;
 #pragma unroll
     for (int q = 0; q < 1024 / (32 * HEAD_SLOTS); ++q) {
         const int e = threadIdx.x + 32 * HEAD_SLOTS * q;            // 1024 = 32 lanes x 32 values
-        const int cc = e >> 5, i = e & 31, o = (i & 15) >> 2, k = i & 3;
         float v = 0.f;
 #pragma unroll
-        for (int sl = 0; sl < HEAD_SLOTS; ++sl) v += red[sl][cc][i];
-        float* dst = nullptr;
-        if (i < 16) dst = o < 3 ? a.gw_crgb + o * 128 + 4 * cc + k : a.gw_a1 + 4 * cc + k;
-        else if (cc < 16) { if (o < 3) dst = a.gw_rgb + o * 64 + 4 * cc + k; }
-        else if (o == 3) dst = a.gw_a + 4 * (cc - 16) + k;
-        if (dst) atomicAdd(dst, v);
+        for (int sl = 0; sl < HEAD_SLOTS; ++sl) v += red[sl][e >> 5][e & 31];
+        __hip_atomic_store(mine + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (threadIdx.x < 8) {
         float v = 0.f;
 #pragma unroll
         for (int sl = 0; sl < HEAD_SLOTS; ++sl) v += redb[sl][threadIdx.x];
-        const int o = threadIdx.x & 3;
-        float* dst = threadIdx.x < 4 ? (o < 3 ? a.gb_crgb + o : a.gb_a1) : (o < 3 ? a.gb_rgb + o : a.gb_a);
-        atomicAdd(dst, v);
+        __hip_atomic_store(mine + 1024 + threadIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // the last block to arrive adds the rows in block order: one atomic per weight
+    __shared__ unsigned last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(a.done, 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    for (int e = threadIdx.x; e < HEAD_VALUES; e += 32 * HEAD_SLOTS) {
+        float v = 0.f;
+        for (unsigned b0 = 0; b0 < gridDim.x; b0 += 16) {                // sixteen rows in flight, added in block order
+            float t[16];
+#pragma unroll
+            for (unsigned u = 0; u < 16; ++u) {
+                const unsigned b = b0 + u < gridDim.x ? b0 + u : gridDim.x - 1;
+                t[u] = __hip_atomic_load(a.partial + (size_t)b * HEAD_VALUES + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 16; ++u) v += b0 + u < gridDim.x ? t[u] : 0.f;
+        }
+        float* dst = nullptr;
+        if (e < 1024) {
+            const int cc = e >> 5, i = e & 31, o = (i & 15) >> 2, k = i & 3;
+            if (i < 16) dst = o < 3 ? a.gw_crgb + o * 128 + 4 * cc + k : a.gw_a1 + 4 * cc + k;
+            else if (cc < 16) { if (o < 3) dst = a.gw_rgb + o * 64 + 4 * cc + k; }
+            else if (o == 3) dst = a.gw_a + 4 * (cc - 16) + k;
+        } else {
+            const int t = e - 1024, o = t & 3;
+            dst = t < 4 ? (o < 3 ? a.gb_crgb + o : a.gb_a1) : (o < 3 ? a.gb_rgb + o : a.gb_a);
+        }
+        if (dst) atomicAdd(dst, v);
     }
 }
 
@@ -539,6 +576,8 @@ struct BwdWork {
     float* gy[6];           // bwd_mode 0: g_y of the six trunk layers (operands of their weight-gradient GEMMs)
     float* wstream_bwd;     // bwd_mode 0: transposed weights as split-bf16 fragments + head table (mlp_bwd_chain.hip)
     unsigned* wg_counters;  // bwd_mode 0: the weight-gradient launch's chunk counters (mlp_wgrad.hip)
+    float* head_partial;    // bwd_mode 1: the head kernel's block sums, [HEAD_MAX_BLOCKS][HEAD_VALUES]
+    unsigned* head_done;    // bwd_mode 1: its arrival counter (zeroed by the call)
 };
 
 static size_t carve_bwd(float* base, int m, int n_dirs, BwdWork* w) {
@@ -557,6 +596,8 @@ static size_t carve_bwd(float* base, int m, int n_dirs, BwdWork* w) {
     for (int l = 0; l < 6; ++l) w->gy[l] = take(M * 128 + 96);
     w->wstream_bwd = take(bwd_chain_stream_floats());
     w->wg_counters = reinterpret_cast<unsigned*>(take(WG_MAX_PAIRS));
+    w->head_partial = take((size_t)HEAD_MAX_BLOCKS * HEAD_VALUES);
+    w->head_done = reinterpret_cast<unsigned*>(take(4));
     return o;
 }
 
@@ -736,8 +777,11 @@ int ucnerf_mlp_bwd(const ucnerf_mlp_bwd_params* bp, void* stream) {
     ha.gw_crgb = G + L.p_crw; ha.gw_a1 = G + L.p_a1w; ha.gw_rgb = G + L.p_rw; ha.gw_a = G + L.p_aw;
     ha.gb_crgb = G + L.p_crb; ha.gb_a1 = G + L.p_a1b; ha.gb_rgb = G + L.p_rb; ha.gb_a = G + L.p_ab;
     {
-        int blocks = cdiv(m, HEAD_SLOTS);                 // one block per CU: the merge is one atomic per weight and block
+        int blocks = cdiv(m, HEAD_SLOTS);                 // one block per CU: the merge reads one row of block sums per block
         if (blocks > device_cus()) blocks = device_cus();
+        if (blocks > HEAD_MAX_BLOCKS) blocks = HEAD_MAX_BLOCKS;
+        ha.partial = w.head_partial; ha.done = w.head_done;
+        if (hipMemsetAsync(w.head_done, 0, sizeof(unsigned), st) != hipSuccess) return fail(UCNERF_EHIP, "mlp_bwd: clearing the head kernel's counter failed");
         hipLaunchKernelGGL(head_bwd_kernel, dim3(blocks), dim3(32 * HEAD_SLOTS), 0, st, ha);
     }
     RUN(check_launch("mlp_bwd head"));
