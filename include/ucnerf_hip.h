@@ -776,8 +776,8 @@ int ucnerf_depth_hypotheses_bwd(const ucnerf_depth_hypotheses_bwd_params* p, voi
 
 /* ------------------------------------------------------------------------------------------------
  * e1   evaluation metrics on the device -- utils/evaluation.py:8-74 (compute_errors, depth_evaluation) and :76-101 (rgb_evaluation: PSNR and
- *      SSIM; LPIPS is a network and not part of this library).  The rendered images and depth maps stay where the render pass left them;
- *      one small vector per call is all a host has to read.
+ *      SSIM; LPIPS below: the library supplies the AlexNet feature stack and the distance, the caller the weights).  The rendered images and
+ *      depth maps stay where the render pass left them; one small vector per call is all a host has to read.
  * ---------------------------------------------------------------------------------------------- */
 /* Workspace of ucnerf_depth_eval and of ucnerf_image_eval on n images of H x W pixels, in floats (the larger of the two: one allocation serves
  * both): the digit histograms of the selection, the per-block partial sums and counts of the reductions.  < 0 on a bad argument. */
@@ -832,6 +832,95 @@ struct ucnerf_image_eval_params {
 };
 typedef struct ucnerf_image_eval_params ucnerf_image_eval_params;
 int ucnerf_image_eval(const ucnerf_image_eval_params* p, void* stream);
+
+/* LPIPS, net = 'alex' (utils/evaluation.py:85-88, :97; the `lpips` package v0.1 on torchvision's AlexNet `features`), inference only, float32,
+ * no atomics: every sum has one fixed order, two calls give the same bits.  (Added to ABI v6; nothing above moved.)
+ *
+ * ucnerf_conv2d_bias_relu: y[n,cout,OH,OW] = relu?(conv2d(x[n,cin,H,W], w[cout,cin,K,K], stride, zero pad) + bias), OH = (H + 2 pad - K) / stride + 1,
+ *   an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulation).  Any cin, cout >= 1; 1 <= K <= 11; cin K K < 2^22;
+ *   cin H W < 2^31; n OH OW < 2^31 - 64.  `packed` is the weight as ucnerf_conv2d_pack wrote it (ucnerf_conv2d_packed_floats(cin, cout, K)
+ *   floats: [cout tile of 64][k padded to a multiple of 32][64] weights, zero where there is none, then one int32 tap code per k).
+ *   ACCUMULATION ORDER over k = (cin K + ky) K + kx: within the j-th run of 32 consecutive k, S_j = the fmaf chain over ascending k from +0;
+ *   then T = (((+0 + S_0) + S_1) + ...) over ascending j; y = T + bias; with relu != 0, y > 0 ? y : +0 (a NaN stays).  A tap that falls into the
+ *   padding is an operand of exactly +0 (so is every k past cin K K): it adds +0, or NaN where its weight is not finite, as torch's does.
+ *   shift / scale (both or neither, [cin]): the input is read as (x - shift[c]) / scale[c] (IEEE division) where it is INSIDE the image; the
+ *   padding stays 0 -- LPIPS' scaling layer in front of a padded convolution.
+ * ucnerf_maxpool2d: 3 x 3 window, stride 2, no pad, floor mode, on `planes` maps of H x W (H, W >= 3): OH = (H - 3) / 2 + 1.  Any float
+ *   values (the first tap starts the maximum, -inf is a value like any other; a NaN in the window is the result, as in torch).
+ * ucnerf_lpips_layer: one launch, one block per pair i.  Per pixel n0 = f0 / (sqrt(sum_c f0^2) + 1e-10), n1 likewise,
+ *   d = sum_c lin[c] (n0[c] - n1[c])^2.  The channel sums are float32 in a fixed order that depends on h w alone: G lanes share a pixel (G = the
+ *   smallest power of two with h w G >= 4096, at most 64), lane g adds the channels g, g + G, ... in ascending order, an xor butterfly folds the
+ *   G partial sums.  The mean of d over the h w pixels is carried in fp64 (lane, wave tree, waves in order) and rounded once;
+ *   out[i] = mean (accumulate == 0) or out[i] + mean (accumulate != 0).  The normalised maps are never stored.  A pixel
+ *   whose features are all zero gives 0 / 1e-10 = 0: it contributes exactly 0.  d(f0, f1) and d(f1, f0) are the same bits.
+ * ucnerf_lpips_alex: the whole chain for n pairs a, b [n,3,H,W] (values in [-1, 1]):
+ *     scaling (in conv1's operand load) -> conv1 3->64 11x11 /4 pad 2 + ReLU = level 0 -> pool -> conv2 64->192 5x5 pad 2 + ReLU = level 1 -> pool
+ *     -> conv3 192->384 3x3 pad 1 + ReLU = level 2 -> conv4 384->256 + ReLU = level 3 -> conv5 256->256 + ReLU = level 4;
+ *     out[i] = ((((d_0 + d_1) + d_2) + d_3) + d_4), d_l = ucnerf_lpips_layer of level l with lin[l].  13 launches; out needs no initial value.
+ *   MINIMUM SIDE 31: conv1 gives o1 = (H - 7) / 4 + 1, the first pool p1 = (o1 - 3) / 2 + 1, conv2 keeps p1, and the second pool needs
+ *   p1 >= 3, so o1 >= 7, (H - 7) / 4 >= 6, H >= 31 (then p1 = 3 and the last three levels are 1 x 1).  A smaller H or W is UCNERF_EINVAL.
+ *   workspace: ucnerf_lpips_workspace_floats(n, H, W) floats (the five levels and the two pooled maps of 2 n images; < 0 on a bad argument);
+ *   every word of it that is read has been written by the same call.
+ * Everywhere: a NULL params or required array and a negative count are UCNERF_EINVAL; n == 0 (planes == 0) is success, nothing launched. */
+struct ucnerf_conv2d_pack_params {
+    int32_t cin, cout, K, reserved;
+    const float* weight;       /* [cout,cin,K,K] */
+    float* packed;             /* ucnerf_conv2d_packed_floats(cin, cout, K) floats, overwritten */
+};
+typedef struct ucnerf_conv2d_pack_params ucnerf_conv2d_pack_params;
+int64_t ucnerf_conv2d_packed_floats(int32_t cin, int32_t cout, int32_t K);
+int ucnerf_conv2d_pack(const ucnerf_conv2d_pack_params* p, void* stream);
+
+struct ucnerf_conv2d_params {
+    int32_t n, cin, H, W, cout, K, stride, pad;
+    int32_t relu;              /* 1: max(y, 0) */
+    int32_t reserved;
+    const float* x;            /* [n,cin,H,W] */
+    const float* packed;       /* from ucnerf_conv2d_pack with the same cin, cout, K */
+    const float* bias;         /* [cout] */
+    const float* shift;        /* [cin] or NULL */
+    const float* scale;        /* [cin] or NULL */
+    float* y;                  /* [n,cout,OH,OW] */
+};
+typedef struct ucnerf_conv2d_params ucnerf_conv2d_params;
+int ucnerf_conv2d_bias_relu(const ucnerf_conv2d_params* p, void* stream);
+
+struct ucnerf_maxpool2d_params {
+    int64_t planes;            /* n * C */
+    int32_t H, W;
+    const float* x;            /* [planes,H,W] */
+    float* y;                  /* [planes,OH,OW] */
+};
+typedef struct ucnerf_maxpool2d_params ucnerf_maxpool2d_params;
+int ucnerf_maxpool2d(const ucnerf_maxpool2d_params* p, void* stream);
+
+struct ucnerf_lpips_layer_params {
+    int32_t n, C, h, w;
+    int32_t accumulate;        /* 0: out[i] = mean d; 1: out[i] += mean d */
+    int32_t reserved;
+    const float* f0;           /* [n,C,h,w] */
+    const float* f1;           /* [n,C,h,w] */
+    const float* lin;          /* [C] */
+    float* out;                /* [n] */
+};
+typedef struct ucnerf_lpips_layer_params ucnerf_lpips_layer_params;
+int ucnerf_lpips_layer(const ucnerf_lpips_layer_params* p, void* stream);
+
+struct ucnerf_lpips_alex_params {
+    int32_t n, H, W, reserved;
+    const float* a;            /* [n,3,H,W] */
+    const float* b;            /* [n,3,H,W] */
+    const float* packed[5];    /* conv1 .. conv5, from ucnerf_conv2d_pack */
+    const float* bias[5];      /* [64], [192], [384], [256], [256] */
+    const float* lin[5];       /* the same lengths */
+    const float* shift;        /* [3] */
+    const float* scale;        /* [3] */
+    float* workspace;          /* ucnerf_lpips_workspace_floats(n, H, W) floats */
+    float* out;                /* [n] */
+};
+typedef struct ucnerf_lpips_alex_params ucnerf_lpips_alex_params;
+int64_t ucnerf_lpips_workspace_floats(int32_t n, int32_t H, int32_t W);
+int ucnerf_lpips_alex(const ucnerf_lpips_alex_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * e2   a whole validation image on the device -- train.py:274-288 (the reference pulls every rendered chunk to the host, concatenates, clamps and

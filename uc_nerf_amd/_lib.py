@@ -182,6 +182,29 @@ class ImageEvalParams(C.Structure):
     _fields_ = [("n", i32), ("H", i32), ("W", i32), ("no_ssim", i32), ("gt", vp), ("pred", vp), ("workspace", vp), ("out", vp)]
 
 
+class Conv2dPackParams(C.Structure):
+    _fields_ = [("cin", i32), ("cout", i32), ("K", i32), ("reserved", i32), ("weight", vp), ("packed", vp)]
+
+
+class Conv2dParams(C.Structure):
+    _fields_ = [("n", i32), ("cin", i32), ("H", i32), ("W", i32), ("cout", i32), ("K", i32), ("stride", i32), ("pad", i32), ("relu", i32),
+                ("reserved", i32), ("x", vp), ("packed", vp), ("bias", vp), ("shift", vp), ("scale", vp), ("y", vp)]
+
+
+class Maxpool2dParams(C.Structure):
+    _fields_ = [("planes", C.c_int64), ("H", i32), ("W", i32), ("x", vp), ("y", vp)]
+
+
+class LpipsLayerParams(C.Structure):
+    _fields_ = [("n", i32), ("C", i32), ("h", i32), ("w", i32), ("accumulate", i32), ("reserved", i32), ("f0", vp), ("f1", vp), ("lin", vp),
+                ("out", vp)]
+
+
+class LpipsAlexParams(C.Structure):
+    _fields_ = [("n", i32), ("H", i32), ("W", i32), ("reserved", i32), ("a", vp), ("b", vp), ("packed", vp * 5), ("bias", vp * 5), ("lin", vp * 5),
+                ("shift", vp), ("scale", vp), ("workspace", vp), ("out", vp)]
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -247,7 +270,10 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_depth_colormap_params": DepthColormapParams,
                  "ucnerf_depth_regress_bwd_values_params": DepthRegressBwdValuesParams,
                  "ucnerf_depth_hypotheses_bwd_params": DepthHypothesesBwdParams,
-                 "ucnerf_composite_fold_params": CompositeFoldParams}
+                 "ucnerf_composite_fold_params": CompositeFoldParams,
+                 "ucnerf_conv2d_pack_params": Conv2dPackParams, "ucnerf_conv2d_params": Conv2dParams,
+                 "ucnerf_maxpool2d_params": Maxpool2dParams, "ucnerf_lpips_layer_params": LpipsLayerParams,
+                 "ucnerf_lpips_alex_params": LpipsAlexParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -322,6 +348,14 @@ SYMBOLS = {
     "ucnerf_eval_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_depth_eval": (C.c_int, [_P, _P]),
     "ucnerf_image_eval": (C.c_int, [_P, _P]),
+    # LPIPS: the AlexNet feature kernels and the distance (additive to ABI v6)
+    "ucnerf_conv2d_packed_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ucnerf_conv2d_pack": (C.c_int, [_P, _P]),
+    "ucnerf_conv2d_bias_relu": (C.c_int, [_P, _P]),
+    "ucnerf_maxpool2d": (C.c_int, [_P, _P]),
+    "ucnerf_lpips_layer": (C.c_int, [_P, _P]),
+    "ucnerf_lpips_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "ucnerf_lpips_alex": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

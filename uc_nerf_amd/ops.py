@@ -1858,6 +1858,141 @@ def image_eval(gt, pred, ssim=True):
     return dict(mse=out[:, 0], psnr=out[:, 1], ssim=out[:, 2], gt_max=out[:, 3], packed=out)
 
 
+# ------------------------------------------------------------------------------------------------ e1: LPIPS
+class PackedConv:
+    """A convolution weight [cout,cin,K,K] in the order `conv2d_bias_relu`'s kernel walks it (made once by `conv2d_pack`)."""
+    __slots__ = ("packed", "cin", "cout", "K")
+
+    def __init__(self, packed, cin, cout, K):
+        self.packed, self.cin, self.cout, self.K = packed, cin, cout, K
+
+
+def conv2d_pack(weight):
+    """Packs a [cout,cin,K,K] float32 device weight (K <= 11) for `conv2d_bias_relu`: one launch, nothing read back."""
+    weight = _f32(weight.detach(), "weight")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or 0 in weight.shape:
+        raise RuntimeError("uc_nerf_amd.conv2d_pack: weight must be [cout,cin,K,K], got %s" % (tuple(weight.shape),))
+    cout, cin, K, _ = weight.shape
+    floats = L.lib().ucnerf_conv2d_packed_floats(cin, cout, K)
+    if floats < 0:
+        raise RuntimeError("uc_nerf_amd.conv2d_pack: %s" % L.lib().ucnerf_last_error().decode())
+    packed = torch.empty(floats, device=weight.device)
+    p = L.Conv2dPackParams()
+    p.cin, p.cout, p.K, p.weight, p.packed = cin, cout, K, _ptr(weight), _ptr(packed)
+    _launch("ucnerf_conv2d_pack", p, weight.device)
+    return PackedConv(packed, cin, cout, K)
+
+
+def conv2d_bias_relu(x, weight, bias, stride=1, pad=0, relu=True, shift=None, scale=None):
+    """relu(conv2d(x, weight, bias, stride, zero padding `pad`)), forward only, exact float32 on the matrix cores (csrc/lpips.hip: the order of
+    the sums is fixed, two calls give the same bits).  x [n,cin,H,W]; weight a `PackedConv` or a [cout,cin,K,K] tensor (packed on the spot);
+    bias [cout].  shift / scale [cin]: the input is read as (x - shift[c]) / scale[c] inside the image, the padding stays zero.  No autograd:
+    inputs that require grad are used detached."""
+    x = _f32(x.detach(), "x")
+    w = weight if isinstance(weight, PackedConv) else conv2d_pack(weight)
+    bias = _f32(bias.detach(), "bias")
+    if x.dim() != 4 or x.shape[1] != w.cin or bias.numel() != w.cout or bias.device != x.device or w.packed.device != x.device:
+        raise RuntimeError("uc_nerf_amd.conv2d_bias_relu: x must be [n,%d,H,W] and bias [%d] on the weight's device, got %s and %s"
+                           % (w.cin, w.cout, tuple(x.shape), tuple(bias.shape)))
+    if (shift is None) != (scale is None):
+        raise RuntimeError("uc_nerf_amd.conv2d_bias_relu: shift and scale go together")
+    if shift is not None:
+        shift, scale = _f32(shift.detach(), "shift"), _f32(scale.detach(), "scale")
+        if shift.numel() != w.cin or scale.numel() != w.cin or shift.device != x.device or scale.device != x.device:
+            raise RuntimeError("uc_nerf_amd.conv2d_bias_relu: shift and scale must be [%d] on x's device" % w.cin)
+    n, _, H, W = x.shape
+    stride, pad = int(stride), int(pad)
+    if stride < 1 or pad < 0 or H + 2 * pad < w.K or W + 2 * pad < w.K:
+        raise RuntimeError("uc_nerf_amd.conv2d_bias_relu: stride=%d pad=%d on a %d x %d input with a %d x %d kernel" % (stride, pad, H, W, w.K, w.K))
+    OH, OW = (H + 2 * pad - w.K) // stride + 1, (W + 2 * pad - w.K) // stride + 1
+    y = torch.empty(n, w.cout, OH, OW, device=x.device)
+    p = L.Conv2dParams()
+    p.n, p.cin, p.H, p.W, p.cout, p.K, p.stride, p.pad, p.relu = n, w.cin, H, W, w.cout, w.K, stride, pad, int(bool(relu))
+    p.x, p.packed, p.bias, p.shift, p.scale, p.y = _ptr(x), _ptr(w.packed), _ptr(bias), _ptr(shift), _ptr(scale), _ptr(y)
+    _launch("ucnerf_conv2d_bias_relu", p, x.device)
+    return y
+
+
+def maxpool2d(x):
+    """max_pool2d(x, 3, 2) (no padding, floor mode) of [n,C,H,W] float32, H, W >= 3; any values, -inf included.  No autograd."""
+    x = _f32(x.detach(), "x")
+    if x.dim() != 4 or x.shape[2] < 3 or x.shape[3] < 3:
+        raise RuntimeError("uc_nerf_amd.maxpool2d: x must be [n,C,H,W] with H, W >= 3, got %s" % (tuple(x.shape),))
+    n, C, H, W = x.shape
+    y = torch.empty(n, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1, device=x.device)
+    p = L.Maxpool2dParams()
+    p.planes, p.H, p.W, p.x, p.y = n * C, H, W, _ptr(x), _ptr(y)
+    _launch("ucnerf_maxpool2d", p, x.device)
+    return y
+
+
+def lpips_layer(f0, f1, lin, out=None):
+    """One feature level of LPIPS in one launch: per pixel n = f / (sqrt(sum_c f^2) + 1e-10) for both maps, d = sum_c lin[c] (n0 - n1)^2, and
+    the mean of d over the pixels -> [n].  f0, f1 [n,C,h,w], lin [C].  With `out` ([n] float32) the mean is ADDED to it in place (the levels
+    of a network in the caller's order) and `out` is returned.  The normalised maps are never stored.  No autograd."""
+    f0, f1, lin = _f32(f0.detach(), "f0"), _f32(f1.detach(), "f1"), _f32(lin.detach(), "lin")
+    if f0.dim() != 4 or f1.shape != f0.shape or f1.device != f0.device or lin.device != f0.device or lin.numel() != f0.shape[1] or 0 in f0.shape[1:]:
+        raise RuntimeError("uc_nerf_amd.lpips_layer: f0, f1 [n,C,h,w] and lin [C] on one device, got %s, %s and %s"
+                           % (tuple(f0.shape), tuple(f1.shape), tuple(lin.shape)))
+    n, C, h, w = f0.shape
+    p = L.LpipsLayerParams()
+    p.accumulate = int(out is not None)
+    if out is None:
+        out = torch.empty(n, device=f0.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == (n,) and out.is_contiguous() and out.device == f0.device):
+        raise RuntimeError("uc_nerf_amd.lpips_layer: out must be a contiguous float32 [%d] tensor on f0's device" % n)
+    p.n, p.C, p.h, p.w = n, C, h, w
+    p.f0, p.f1, p.lin, p.out = _ptr(f0), _ptr(f1), _ptr(lin), _ptr(out)
+    _launch("ucnerf_lpips_layer", p, f0.device)
+    return out
+
+
+def lpips_workspace_floats(n, H, W):
+    floats = L.lib().ucnerf_lpips_workspace_floats(n, H, W)
+    if floats < 0:
+        raise RuntimeError("uc_nerf_amd: lpips workspace: %s" % L.lib().ucnerf_last_error().decode())
+    return int(floats)
+
+
+def lpips_alex(a, b, convs, biases, lins, shift, scale, workspace=None):
+    """The whole LPIPS(net='alex') chain for n pairs a, b [n,3,H,W] float32 in [-1, 1] (H, W >= 31) -> [n] on the device, nothing read back.
+    convs: five `PackedConv` (conv1 .. conv5 of AlexNet's features); biases, lins: five vectors each; shift, scale [3].  `workspace`: a float32
+    tensor of at least lpips_workspace_floats(n, H, W) elements (allocated when None); its contents do not matter.  No autograd."""
+    a, b = _f32(a.detach(), "a"), _f32(b.detach(), "b")
+    if a.dim() != 4 or a.shape[1] != 3 or b.shape != a.shape or b.device != a.device:
+        raise RuntimeError("uc_nerf_amd.lpips_alex: a and b must be [n,3,H,W] on one device, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    geometry = ((3, 64, 11), (64, 192, 5), (192, 384, 3), (384, 256, 3), (256, 256, 3))
+    if len(convs) != 5 or len(biases) != 5 or len(lins) != 5:
+        raise RuntimeError("uc_nerf_amd.lpips_alex: five convolutions, biases and lin vectors")
+    dev = a.device
+    n, _, H, W = a.shape
+    p = L.LpipsAlexParams()
+    keep = []
+    for l, (cin, cout, K) in enumerate(geometry):
+        c = convs[l]
+        if not isinstance(c, PackedConv) or (c.cin, c.cout, c.K) != (cin, cout, K) or c.packed.device != dev:
+            raise RuntimeError("uc_nerf_amd.lpips_alex: convolution %d must be a PackedConv of %d -> %d, %d x %d on the images' device" % (l + 1, cin, cout, K, K))
+        bl, ll = _f32(biases[l].detach(), "bias"), _f32(lins[l].detach(), "lin")
+        if bl.numel() != cout or ll.numel() != cout or bl.device != dev or ll.device != dev:
+            raise RuntimeError("uc_nerf_amd.lpips_alex: bias and lin of level %d must be [%d] on the images' device" % (l, cout))
+        keep += [bl, ll]
+        p.packed[l], p.bias[l], p.lin[l] = _ptr(c.packed), _ptr(bl), _ptr(ll)
+    shift, scale = _f32(shift.detach(), "shift"), _f32(scale.detach(), "scale")
+    if shift.numel() != 3 or scale.numel() != 3 or shift.device != dev or scale.device != dev:
+        raise RuntimeError("uc_nerf_amd.lpips_alex: shift and scale must be [3] on the images' device")
+    floats = lpips_workspace_floats(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(floats, device=dev)
+    elif not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.dtype == torch.float32 and workspace.is_contiguous()
+              and workspace.device == dev and workspace.numel() >= floats):
+        raise RuntimeError("uc_nerf_amd.lpips_alex: workspace must be a contiguous float32 tensor of at least %d elements on the images' device" % floats)
+    out = torch.empty(n, device=dev)
+    p.n, p.H, p.W = n, H, W
+    p.a, p.b, p.shift, p.scale, p.workspace, p.out = _ptr(a), _ptr(b), _ptr(shift), _ptr(scale), _ptr(workspace), _ptr(out)
+    _launch("ucnerf_lpips_alex", p, dev)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ e2
 def image_group_pixels():
     """Pixels one workgroup of the image kernels covers (and folds into one atomicMin / atomicMax)."""

@@ -5,6 +5,10 @@ with cv2 + PIL.  Here a chunk goes from `rendering()` straight into the image pl
 one launch), the depth pictures are one launch each (ucnerf_depth_colormap), and everything returned is a device tensor that
 `utils.evaluation.rgb_evaluation` / `depth_evaluation` take as it is -- a validation image costs the one small read those make.
 Nothing in this module reads the device back.
+
+All three metrics of a validation epoch from the images this module returns (LPIPS needs the two checkpoints, nothing else):
+    lpips_fn = uc_nerf_amd.utils.evaluation.LPIPS.from_files(alexnet_path, lpips_alex_lin_path)      # once; packs the weights
+    psnr, ssim, lpips = rgb_evaluation(torch.stack(gt_rgbs), torch.stack(pred_rgbs), savedir, lpips_fn=lpips_fn)
 """
 import torch
 
