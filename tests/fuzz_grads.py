@@ -136,7 +136,7 @@ class DevicePass:
         kept = {}
         for i, name in enumerate(ops.KEPT_SETS):
             chunk = ws[off + i * per: off + (i + 1) * per]
-            kept[name] = (ops.decode_p24(chunk, M) if ops._backward_mode == 0 else chunk[: M * 128].view(M, 128)).cpu()
+            kept[name] = (ops.decode_p24(chunk, M) if ops.backward_mode() == "chain" else chunk[: M * 128].view(M, 128)).cpu()
         sides = [(kept["h%d" % k] > 0).view(n, S, 128) for k in range(6)]
         sides += [(kept["vc"][:, :64] > 0).view(n, S, 64), (kept["vc"][:, 64:] > 0).view(n, S, 64), (out["raw"][..., 3:4] > 0).cpu()]
         res = self.rp.backward(rd, zz, out, r3.to(dev).contiguous(), r1.to(dev).contiguous(), self.flat, coords=coords, f32_weights=self.f32w)

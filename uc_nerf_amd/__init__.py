@@ -2,7 +2,15 @@
 
 Layers:
   csrc/ + include/ucnerf_hip.h   hand-written HIP kernels behind a C ABI (libucnerf_hip.so)
-  _lib.py, ops.py                ctypes binding and torch-tensor wrappers (plumbing)
+  _lib.py, ops/                  ctypes binding and torch-tensor wrappers (plumbing); ops re-exports its modules' names:
+    ops/_core.py                   argument checks, current stream / device, the launch path, Event
+    ops/rays.py                    ray generation, sampling, NDC projection, the one-launch ray builders, embed
+    ops/gather.py                  GatherSources, channel-last views and repack, gather forward / backward
+    ops/network.py                 the MLP: backward mode, split operand and guard (their one home), PackedWeights, forward / backward
+    ops/compositing.py             compositing (plain, merged, *_maps), the gradient fold, sample_pdf, merge_rows
+    ops/mvs.py                     cost volume, depth regression, depth hypotheses, the cascade loss
+    ops/metrics.py                 depth / image metrics, LPIPS, the validation-image ops
+    ops/render.py                  RenderPass
   network/, utils/, data/        mirrors of the reference's Python call surface for this path
   pipeline.py, parallel.py       the fused coarse+fine renderer and ray-sharded multi-GPU driver
 
