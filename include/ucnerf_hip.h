@@ -922,6 +922,49 @@ typedef struct ucnerf_lpips_alex_params ucnerf_lpips_alex_params;
 int64_t ucnerf_lpips_workspace_floats(int32_t n, int32_t H, int32_t W);
 int ucnerf_lpips_alex(const ucnerf_lpips_alex_params* p, void* stream);
 
+/* The 3-D convolutions of CasMVSNet's cost regularisation (network/mvs_models.py:110-195 Conv3d / Deconv3d, :412-443 CostRegNet), inference only,
+ * float32, NCDHW contiguous in and out, no atomics: every sum has one fixed order, two calls give the same bits and an image's result does not
+ * depend on the batch it is in.  (Added to ABI v6; nothing above moved.)
+ *
+ * ucnerf_conv3d: y = act(conv(x) + bias[co]) (+ skip); act = max(., 0) with relu != 0 (a NaN stays), the identity otherwise; skip (NULL or a
+ *   tensor of y's shape) is added AFTER the activation.  An implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation):
+ *   16-row channel tiles for cout <= 16, 32-row tiles above; cout == 1 of the forward form runs as a VALU kernel in the same order.
+ *   transposed == 0: y[n,cout,OD,OH,OW], O = (I + 2 pad - K) / stride + 1, cubic K of 1 or 3, stride 1 or 2, zero padding 0 <= pad <= 64,
+ *     weight [cout,cin,K,K,K].
+ *   transposed == 1: conv_transpose3d with K = 3, stride = 2, pad = 1, output_padding = 1 (no other), weight [cin,cout,3,3,3]; y[n,cout,2D,2H,2W].
+ *     The output voxels are handled in 8 parity classes (od & 1, oh & 1, ow & 1); a class multiplies only its 1, 2, 4 or 8 live taps.
+ *   `packed` is the weight as ucnerf_conv3d_pack wrote it, `packed_floats` its size = ucnerf_conv3d_packed_floats(cin, cout, K, transposed): per
+ *     class [channel tile][k padded to a multiple of 32][16 or 32 rows] weights, zero where there is none, then one int32 tap code per k.
+ *   Limits: cin <= 2^16; cin D H W, cout OD OH OW < 2^31; n * voxels < 2^31 - 1024.
+ *   ACCUMULATION ORDER: k = ci * taps + t, t = (kd K + kh) K + kw (the flat index of the weight's row; for the transposed form the live taps of the
+ *     class in that same order).  Within the j-th run of 32 consecutive k, S_j = the fmaf chain over ascending k from +0; then
+ *     T = (((+0 + S_0) + S_1) + ...) over ascending j; y = T + bias; the activation; then + skip.  A tap outside the volume contributes +0.
+ *   UCNERF_EINVAL before any device call: NULL params or required array, negative n, non-positive cin / cout / D / H / W, a K / stride / pad /
+ *     transposed combination outside the above, packed_floats that does not match.  n == 0 is success, nothing launched. */
+struct ucnerf_conv3d_pack_params {
+    int32_t cin, cout, K, transposed;
+    const float* weight;       /* [cout,cin,K,K,K], transposed: [cin,cout,3,3,3] */
+    float* packed;             /* ucnerf_conv3d_packed_floats(cin, cout, K, transposed) floats, overwritten */
+};
+typedef struct ucnerf_conv3d_pack_params ucnerf_conv3d_pack_params;
+int64_t ucnerf_conv3d_packed_floats(int32_t cin, int32_t cout, int32_t K, int32_t transposed);   /* < 0 on a bad argument */
+int ucnerf_conv3d_pack(const ucnerf_conv3d_pack_params* p, void* stream);
+
+struct ucnerf_conv3d_params {
+    int32_t n, cin, D, H, W, cout, K, stride, pad;
+    int32_t relu;              /* 1: max(y, 0) */
+    int32_t transposed;        /* 1: the transposed form */
+    int32_t reserved;
+    int64_t packed_floats;     /* floats `packed` holds */
+    const float* x;            /* [n,cin,D,H,W] */
+    const float* packed;       /* from ucnerf_conv3d_pack with the same cin, cout, K, transposed */
+    const float* bias;         /* [cout] */
+    const float* skip;         /* y's shape, or NULL */
+    float* y;                  /* [n,cout,OD,OH,OW] */
+};
+typedef struct ucnerf_conv3d_params ucnerf_conv3d_params;
+int ucnerf_conv3d(const ucnerf_conv3d_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * e2   a whole validation image on the device -- train.py:274-288 (the reference pulls every rendered chunk to the host, concatenates, clamps and
  *      permutes there) and utils/utils.py:58-77 (visualize_depth: numpy normalisation, cv2.applyColorMap, PIL, ToTensor).  Here a chunk is

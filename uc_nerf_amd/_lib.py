@@ -205,6 +205,15 @@ class LpipsAlexParams(C.Structure):
                 ("shift", vp), ("scale", vp), ("workspace", vp), ("out", vp)]
 
 
+class Conv3dPackParams(C.Structure):
+    _fields_ = [("cin", i32), ("cout", i32), ("K", i32), ("transposed", i32), ("weight", vp), ("packed", vp)]
+
+
+class Conv3dParams(C.Structure):
+    _fields_ = [("n", i32), ("cin", i32), ("D", i32), ("H", i32), ("W", i32), ("cout", i32), ("K", i32), ("stride", i32), ("pad", i32), ("relu", i32),
+                ("transposed", i32), ("reserved", i32), ("packed_floats", C.c_int64), ("x", vp), ("packed", vp), ("bias", vp), ("skip", vp), ("y", vp)]
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -273,7 +282,8 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_composite_fold_params": CompositeFoldParams,
                  "ucnerf_conv2d_pack_params": Conv2dPackParams, "ucnerf_conv2d_params": Conv2dParams,
                  "ucnerf_maxpool2d_params": Maxpool2dParams, "ucnerf_lpips_layer_params": LpipsLayerParams,
-                 "ucnerf_lpips_alex_params": LpipsAlexParams}
+                 "ucnerf_lpips_alex_params": LpipsAlexParams,
+                 "ucnerf_conv3d_pack_params": Conv3dPackParams, "ucnerf_conv3d_params": Conv3dParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -356,6 +366,10 @@ SYMBOLS = {
     "ucnerf_lpips_layer": (C.c_int, [_P, _P]),
     "ucnerf_lpips_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_lpips_alex": (C.c_int, [_P, _P]),
+    # the 3-D convolutions of the cost regularisation (additive to ABI v6)
+    "ucnerf_conv3d_packed_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "ucnerf_conv3d_pack": (C.c_int, [_P, _P]),
+    "ucnerf_conv3d": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

@@ -19,6 +19,9 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // D = A * B + C on 32x32 tiles: fp32 operands (one k per lane), or eight bf16 / fp16 operands per lane (k16)
 __device__ __forceinline__ f32x16 mfma_32x32x2(float a, float b, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+// D = A * B + C on a 16x16 tile, fp32 operands, four k per instruction: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][column l & 15];
+// register r of the result is row 4 (l >> 4) + r, column l & 15
+__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma_32x32x16(const bf16x8& a, const bf16x8& b, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 mfma_32x32x16(const f16x8& a, const f16x8& b, const f32x16& c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 

@@ -445,6 +445,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_depth_regress_bwd_values_params); SZ(ucnerf_depth_hypotheses_bwd_params);
     SZ(ucnerf_composite_fold_params);
     SZ(ucnerf_conv2d_pack_params); SZ(ucnerf_conv2d_params); SZ(ucnerf_maxpool2d_params); SZ(ucnerf_lpips_layer_params); SZ(ucnerf_lpips_alex_params);
+    SZ(ucnerf_conv3d_pack_params); SZ(ucnerf_conv3d_params);
 #undef SZ
     return -1;
 }

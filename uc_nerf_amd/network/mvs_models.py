@@ -3,8 +3,10 @@ path: `DepthNet` (mvs_models.py:585-646), the depth-hypothesis helpers `get_dept
 `get_cur_depth_range_samples` (:536-573) and the three-stage loop `CascadeMVSNet` (:648-762).  Same call signatures and
 result keys; the cost-volume assembly (`homo_warp` + mask count + variance), the depth regression and the link between
 two stages (previous depth -> next stage's hypothesis volume) run as the HIP kernels `ucnerf_cost_volume` /
-`ucnerf_depth_regress` / `ucnerf_depth_hypotheses`; the CNNs -- the feature pyramid and the 3D regularisation networks --
-stay the caller's modules (MIOpen territory).
+`ucnerf_depth_regress` / `ucnerf_depth_hypotheses`.  The CNNs -- the feature pyramid `FeatureNet` (:309-410) and the 3-D
+regularisation network `CostRegNet` (:412-443) -- are mirrored here with the reference's parameter names: they train through torch's
+layers and, under eval() + no_grad, run on `ucnerf_conv2d_bias_relu` / `ucnerf_conv3d` with the batch-norms folded into the weights.
+`CascadeMVSNet(...)` still takes the caller's modules; `CascadeMVSNet.with_cnns(...)` builds its own.
 
 The cost volume and the regression have backward kernels behind `torch.autograd.Function`s, so the feature network
 trains through the variance volume and the regularisation network through depth and photometric confidence, as in the
@@ -20,6 +22,248 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+
+
+INFERENCE_ROUTES = ("device", "torch")
+
+
+class Conv2d(nn.Module):
+    """mvs_models.py:21-61: conv (bias only without bn) -> BatchNorm2d -> ReLU."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, relu=True, bn=True, bn_momentum=0.1, **kwargs):
+        super().__init__()
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
+        self.kernel_size, self.stride = kernel_size, stride
+        self.bn = nn.BatchNorm2d(out_channels, momentum=bn_momentum) if bn else None
+        self.relu = relu
+
+    def forward(self, x):
+        x = self.conv(x)
+        if self.bn is not None:
+            x = self.bn(x)
+        return F.relu(x) if self.relu else x
+
+
+class Conv3d(nn.Module):
+    """mvs_models.py:110-152: conv (bias only without bn) -> BatchNorm3d -> ReLU."""
+    transposed = False
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1, **kwargs):
+        super().__init__()
+        if stride not in (1, 2):
+            raise AssertionError("stride 1 or 2")
+        self.out_channels, self.kernel_size, self.stride = out_channels, kernel_size, stride
+        self.conv = nn.Conv3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
+        self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
+        self.relu = relu
+
+    def forward(self, x):
+        x = self.conv(x)
+        if self.bn is not None:
+            x = self.bn(x)
+        return F.relu(x) if self.relu else x
+
+
+class Deconv3d(nn.Module):
+    """mvs_models.py:154-195: transposed conv (bias only without bn) -> BatchNorm3d -> ReLU."""
+    transposed = True
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1, **kwargs):
+        super().__init__()
+        if stride not in (1, 2):
+            raise AssertionError("stride 1 or 2")
+        self.out_channels, self.kernel_size, self.stride = out_channels, kernel_size, stride
+        self.conv = nn.ConvTranspose3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
+        self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
+        self.relu = relu
+
+    def forward(self, x):
+        x = self.conv(x)
+        if self.bn is not None:
+            x = self.bn(x)
+        return F.relu(x) if self.relu else x
+
+
+def fold_conv_bn(layer, dtype=torch.float64):
+    """(w', b') of one layer with its eval-mode batch-norm folded in, computed in `dtype`: per output channel s = gamma / sqrt(running_var + eps),
+    w' = w s, b' = beta - running_mean s (+ the convolution's own bias times s, where it has one).  `layer` is a Conv2d / Conv3d / Deconv3d above
+    or a bare nn.Conv*: then w' = w and b' = its bias or zeros.  The output channel is dimension 1 of a transposed convolution's weight."""
+    conv, bn = (layer.conv, layer.bn) if hasattr(layer, "conv") else (layer, None)
+    w = conv.weight.detach().to(dtype)
+    cout_dim = 1 if isinstance(conv, nn.ConvTranspose3d) else 0
+    cout = w.shape[cout_dim]
+    b = conv.bias.detach().to(dtype) if conv.bias is not None else torch.zeros(cout, dtype=dtype, device=w.device)
+    if bn is None:
+        return w, b
+    s = bn.weight.detach().to(dtype) / torch.sqrt(bn.running_var.detach().to(dtype) + bn.eps)
+    shape = [1] * w.dim()
+    shape[cout_dim] = cout
+    return w * s.view(shape), bn.bias.detach().to(dtype) + (b - bn.running_mean.detach().to(dtype)) * s
+
+
+class _InferenceCache:
+    """What the device route made of a module's parameters and buffers (folded, packed weights), valid while every one of them is the tensor
+    it was made from, at the version and on the device it had then.  The cache keeps the tensors themselves: an object it holds cannot be
+    freed and its address reused by another, so identity is a sound test (an address is not: README, round 5)."""
+
+    def __init__(self):
+        self.sources, self.stamps, self.value = None, None, None
+
+    @staticmethod
+    def _stamp(t):
+        return (t._version, t.device, t.dtype)
+
+    def get(self, module, build):
+        now = list(module.parameters()) + list(module.buffers())
+        if (self.sources is None or len(now) != len(self.sources)
+                or any(a is not b or self._stamp(a) != s for a, b, s in zip(now, self.sources, self.stamps))):
+            self.value = build()
+            self.sources, self.stamps = now, [self._stamp(t) for t in now]
+        return self.value
+
+
+def _check_route(inference):
+    if inference not in INFERENCE_ROUTES:
+        raise ValueError("uc_nerf_amd: inference=%r -- \"device\" (the HIP kernels under eval() + no_grad) or \"torch\"" % (inference,))
+    return inference
+
+
+def _device_route(module, x):
+    return module.inference == "device" and not module.training and not torch.is_grad_enabled() and x.is_cuda
+
+
+class FeatureNet(nn.Module):
+    """mvs_models.py:309-410, the "fpn" pyramid with three stages: image [n,3,H,W] -> {"stage1": [n,4c,H/4,W/4], "stage2": [n,2c,H/2,W/2],
+    "stage3": [n,c,H,W]}.  Parameter and buffer names are the reference's, so a checkpoint's `feature.*` keys load strictly.
+    Two routes: torch's layers whenever grad is enabled, the module is in training mode or the input is not on a ROCm device; with
+    inference="device", under eval() + no_grad, `ops.conv2d_bias_relu` with the batch-norms folded into weights and biases (packed once, cached)."""
+
+    def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device"):
+        super().__init__()
+        if arch_mode != "fpn" or num_stage != 3:
+            raise NotImplementedError("uc_nerf_amd FeatureNet: arch_mode=%r num_stage=%r -- only arch_mode=\"fpn\" with num_stage=3 is built"
+                                      % (arch_mode, num_stage))
+        self.arch_mode, self.stride, self.base_channels, self.num_stage = arch_mode, stride, base_channels, num_stage
+        self.inference = _check_route(inference)
+        c = base_channels
+        self.conv0 = nn.Sequential(Conv2d(3, c, 3, 1, padding=1), Conv2d(c, c, 3, 1, padding=1))
+        self.conv1 = nn.Sequential(Conv2d(c, 2 * c, 5, stride=2, padding=2), Conv2d(2 * c, 2 * c, 3, 1, padding=1), Conv2d(2 * c, 2 * c, 3, 1, padding=1))
+        self.conv2 = nn.Sequential(Conv2d(2 * c, 4 * c, 5, stride=2, padding=2), Conv2d(4 * c, 4 * c, 3, 1, padding=1), Conv2d(4 * c, 4 * c, 3, 1, padding=1))
+        self.out1 = nn.Conv2d(4 * c, 4 * c, 1, bias=False)
+        self.inner1 = nn.Conv2d(2 * c, 4 * c, 1, bias=True)
+        self.inner2 = nn.Conv2d(c, 4 * c, 1, bias=True)
+        self.out2 = nn.Conv2d(4 * c, 2 * c, 3, padding=1, bias=False)
+        self.out3 = nn.Conv2d(4 * c, c, 3, padding=1, bias=False)
+        self.out_channels = [4 * c, 2 * c, c]
+        self._cache = _InferenceCache()
+
+    def _layers(self):
+        return list(self.conv0) + list(self.conv1) + list(self.conv2) + [self.out1, self.inner1, self.inner2, self.out2, self.out3]
+
+    def _fold(self):
+        out = []
+        for layer in self._layers():
+            w, b = fold_conv_bn(layer)
+            out.append((ops.conv2d_pack(w.float()), b.float().contiguous()))
+        return out
+
+    def forward(self, x):
+        if _device_route(self, x):
+            return self._forward_device(x)
+        conv0 = self.conv0(x)
+        conv1 = self.conv1(conv0)
+        conv2 = self.conv2(conv1)
+        outputs = {"stage1": self.out1(conv2)}
+        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + self.inner1(conv1)
+        outputs["stage2"] = self.out2(intra)
+        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + self.inner2(conv0)
+        outputs["stage3"] = self.out3(intra)
+        return outputs
+
+    def _forward_device(self, x):
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
+            raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
+                               "it), got %s" % (tuple(x.shape),))
+        folded = self._cache.get(self, self._fold)
+        layers = self._layers()
+
+        def run(i, t, relu):
+            conv = layers[i].conv if hasattr(layers[i], "conv") else layers[i]
+            return ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=relu)
+
+        conv0 = run(1, run(0, x, True), True)
+        conv1 = run(4, run(3, run(2, conv0, True), True), True)
+        conv2 = run(7, run(6, run(5, conv1, True), True), True)
+        outputs = {"stage1": run(8, conv2, False)}
+        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + run(9, conv1, False)
+        outputs["stage2"] = run(11, intra, False)
+        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0, False)
+        outputs["stage3"] = run(12, intra, False)
+        return outputs
+
+
+class CostRegNet(nn.Module):
+    """mvs_models.py:412-443: variance volume [n,C,D,H,W] -> (cost [n,c,D,H,W], logits [n,1,D,H,W]); an hourglass of seven convolutions, three
+    transposed ones with skip additions and the one-channel `prob`.  Names as in the reference, so `cost_regularization.N.*` keys load strictly.
+    Two routes as in FeatureNet; the device route is eleven `ops.conv3d` launches (batch-norm folded, the skip additions inside the launches)
+    and needs D, H and W divisible by 8 -- as the reference's additions do."""
+
+    ORDER = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11", "prob")
+
+    def __init__(self, in_channels, base_channels, inference="device"):
+        super().__init__()
+        self.inference = _check_route(inference)
+        c = base_channels
+        self.conv0 = Conv3d(in_channels, c, padding=1)
+        self.conv1 = Conv3d(c, 2 * c, stride=2, padding=1)
+        self.conv2 = Conv3d(2 * c, 2 * c, padding=1)
+        self.conv3 = Conv3d(2 * c, 4 * c, stride=2, padding=1)
+        self.conv4 = Conv3d(4 * c, 4 * c, padding=1)
+        self.conv5 = Conv3d(4 * c, 8 * c, stride=2, padding=1)
+        self.conv6 = Conv3d(8 * c, 8 * c, padding=1)
+        self.conv7 = Deconv3d(8 * c, 4 * c, stride=2, padding=1, output_padding=1)
+        self.conv9 = Deconv3d(4 * c, 2 * c, stride=2, padding=1, output_padding=1)
+        self.conv11 = Deconv3d(2 * c, c, stride=2, padding=1, output_padding=1)
+        self.prob = nn.Conv3d(c, 1, 3, stride=1, padding=1, bias=False)
+        self._cache = _InferenceCache()
+
+    def _fold(self):
+        out = {}
+        for name in self.ORDER:
+            layer = getattr(self, name)
+            w, b = fold_conv_bn(layer)
+            out[name] = (ops.conv3d_pack(w.float(), transposed=getattr(layer, "transposed", False)), b.float().contiguous())
+        return out
+
+    def forward(self, x):
+        if _device_route(self, x):
+            return self._forward_device(x)
+        conv0 = self.conv0(x)
+        conv2 = self.conv2(self.conv1(conv0))
+        conv4 = self.conv4(self.conv3(conv2))
+        x = self.conv6(self.conv5(conv4))
+        x = conv4 + self.conv7(x)
+        x = conv2 + self.conv9(x)
+        cost = conv0 + self.conv11(x)
+        return cost, self.prob(cost)
+
+    def _forward_device(self, x):
+        if x.dim() != 5 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
+            raise RuntimeError("uc_nerf_amd CostRegNet: the device route takes [n,C,D,H,W] with D, H and W divisible by 8 (three halvings, three "
+                               "doublings and the skip additions between them), got %s" % (tuple(x.shape),))
+        f = self._cache.get(self, self._fold)
+
+        def conv(name, t, stride=1, skip=None, relu=True):
+            return ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=relu, skip=skip, transposed=f[name][0].transposed)
+
+        conv0 = conv("conv0", x)
+        conv2 = conv("conv2", conv("conv1", conv0, 2))
+        conv4 = conv("conv4", conv("conv3", conv2, 2))
+        x = conv("conv6", conv("conv5", conv4, 2))
+        x = conv("conv7", x, 2, skip=conv4)
+        x = conv("conv9", x, 2, skip=conv2)
+        cost = conv("conv11", x, 2, skip=conv0)
+        return cost, conv("prob", cost, relu=False)
 
 
 def mvs_depth_regression(p, depth_values):                 # mvs_models.py:574-579
@@ -131,6 +375,19 @@ class CascadeMVSNet(nn.Module):
                 cost_regularization = nn.ModuleList(cost_regularization)
         self.cost_regularization = cost_regularization
         self.DepthNet = DepthNet()
+
+    @classmethod
+    def with_cnns(cls, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
+                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device"):
+        """The net with its own `FeatureNet` and one `CostRegNet` per stage (mvs_models.py:678-687), so that a reference checkpoint loads and
+        runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch")."""
+        if share_cr:
+            raise NotImplementedError("uc_nerf_amd CascadeMVSNet.with_cnns: share_cr=True (one regulariser for stages whose feature channels "
+                                      "differ; the reference's constructor fails on it too) -- hand a module in through CascadeMVSNet(...)")
+        feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference)
+        regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference)
+                              for i in range(len(ndepths))])
+        return cls(view_num, ndepths, depth_interals_ratio, share_cr, grad_method, arch_mode, cr_base_chs, feature=feature, cost_regularization=regs)
 
     def forward(self, imgs, affine_mat, affine_mat_inv, near_far, pad):
         if imgs.shape[0] != 1:
