@@ -965,6 +965,65 @@ struct ucnerf_conv3d_params {
 typedef struct ucnerf_conv3d_params ucnerf_conv3d_params;
 int ucnerf_conv3d(const ucnerf_conv3d_params* p, void* stream);
 
+/* Batch-statistic batch-norm: what nn.BatchNorm2d / 3d computes in training mode, forward only, for the CNNs above under train() + no_grad (the
+ * reference's validation_step runs its consistency learner that way, train.py:226-243).  (Added to ABI v6; nothing above moved.)
+ * y is a contiguous float32 [n, C, S] tensor, S the product of the spatial sizes; a channel has N = n S values, numbered i = img * S + offset.
+ * Two launches, ucnerf_bn_stats then ucnerf_bn_apply, on one stream; nothing is read back, no atomics, every store a plain vector store: two
+ * calls give the same bits, and the pair can sit inside a captured graph.
+ *
+ * ucnerf_bn_partials(n, S) = P = min(32, ceil(N / 4096)), the partial slots per channel; < 0 on a bad argument (n or S < 1, N < 2 or above the
+ *   limit below).  Pure host.  Slice j of a channel is the values [j L, min((j + 1) L, N)) with L = ceil(N / P) rounded up to a multiple of 4;
+ *   every slice is non-empty, the last may be shorter.
+ * ucnerf_bn_stats: workspace[(c P + j) * 3 + 0 .. 2] = (count, mean, M2) of slice j of channel c as float64, M2 = sum (y - mean)^2.
+ *   SUMMATION ORDER, all in float64, the values converted exactly.  merge(a, b), Chan's pairwise update: b empty -> a; otherwise n = na + nb,
+ *   r = nb / n, d = mean_b - mean_a, mean = mean_a + d r, M2 = (M2_a + M2_b) + (d d)(na r), separate multiplications and additions.
+ *   The slice is walked in quads of four consecutive values, quad q at j L + 4 q.  Thread t of 1024 takes, as its k-th chunk, the quads
+ *   (4 k + u) 1024 + t, u = 0 .. 3: over the chunk's values inside the slice, in ascending i, sum = (((0 + v) + v) + ...), mean = sum / count, then
+ *   M2 = (((0 + (v - mean)^2) + ...) in the same order; the thread's triple = merge(merge(merge(empty, chunk 0), chunk 1), ...).  Lanes: for
+ *   d = 1, 2, 4, 8, 16, 32 lane l < 64 - d becomes merge(lane l, lane l + d) with the values of before the step; lane 0 holds the wave's triple.
+ *   Waves: merge(.. merge(wave 0, wave 1) .., wave 15).
+ * ucnerf_bn_apply: every block folds merge(.. merge(triple 0, triple 1) .., triple P - 1) of its channel, in float64, and so holds the same
+ *   mu = mean and sigma^2 = M2 / N (biased), each rounded ONCE to float32.  Then in float32: s = weight[c] / sqrt(sigma^2 + eps), IEEE division
+ *   and square root; out = act(fma(y - mu, s, bias[c])) (+ skip), act = max(., 0) with relu != 0 (a NaN stays), the identity otherwise; skip
+ *   (NULL or a tensor of y's shape) is added AFTER the activation.  out may be y itself (not a shifted overlap).  One block per channel also
+ *   writes saved_mean[c] = mu, saved_var[c] = sigma^2, running_mean[c] = (1 - m) running_mean[c] + m mu and running_var[c] =
+ *   (1 - m) running_var[c] + m u, u = M2 / (N - 1) rounded once to float32 (the unbiased variance), in float32 with separate multiplications
+ *   and additions; one thread of the launch adds 1 to the int64 *num_batches_tracked.
+ * Both are memory-bound: stats reads |y| once, apply reads |y| (+ |skip|) and writes |y|; accesses are 16 bytes per lane where S % 4 == 0 and
+ *   the arrays are 16-byte aligned, 4 bytes otherwise (the same values in the same order either way).
+ * UCNERF_EINVAL before any device call: NULL params or required array, n / C / S < 1, N < 2, N > 2^31 - 2^20, C > 65535, a product that
+ *   overflows, eps <= 0, momentum outside (0, 1], workspace_triples < C P, a workspace or num_batches_tracked that is not 8-byte aligned. */
+int64_t ucnerf_bn_partials(int64_t n, int64_t S);
+struct ucnerf_bn_stats_params {
+    int64_t n, C, S;
+    int64_t workspace_triples; /* triples (3 float64 each) the workspace holds, at least C P */
+    const float* y;            /* [n,C,S] */
+    double* workspace;         /* [C,P,3], overwritten */
+};
+typedef struct ucnerf_bn_stats_params ucnerf_bn_stats_params;
+int ucnerf_bn_stats(const ucnerf_bn_stats_params* p, void* stream);
+
+struct ucnerf_bn_apply_params {
+    int64_t n, C, S;
+    int64_t workspace_triples;
+    float eps, momentum;
+    int32_t relu;              /* 1: max(., 0) before the skip addition */
+    int32_t reserved;
+    const float* y;            /* [n,C,S], as ucnerf_bn_stats read it */
+    const double* workspace;   /* as ucnerf_bn_stats wrote it for the same n, C, S */
+    const float* weight;       /* gamma [C] */
+    const float* bias;         /* beta [C] */
+    const float* skip;         /* y's shape, or NULL */
+    float* out;                /* y's shape; may be y */
+    float* saved_mean;         /* [C], overwritten */
+    float* saved_var;          /* [C], overwritten: the biased variance */
+    float* running_mean;       /* [C], updated */
+    float* running_var;        /* [C], updated with the unbiased variance */
+    int64_t* num_batches_tracked;   /* one int64 on the device, incremented */
+};
+typedef struct ucnerf_bn_apply_params ucnerf_bn_apply_params;
+int ucnerf_bn_apply(const ucnerf_bn_apply_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * e2   a whole validation image on the device -- train.py:274-288 (the reference pulls every rendered chunk to the host, concatenates, clamps and
  *      permutes there) and utils/utils.py:58-77 (visualize_depth: numpy normalisation, cv2.applyColorMap, PIL, ToTensor).  Here a chunk is

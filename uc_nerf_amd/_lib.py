@@ -214,6 +214,16 @@ class Conv3dParams(C.Structure):
                 ("transposed", i32), ("reserved", i32), ("packed_floats", C.c_int64), ("x", vp), ("packed", vp), ("bias", vp), ("skip", vp), ("y", vp)]
 
 
+class BnStatsParams(C.Structure):
+    _fields_ = [("n", C.c_int64), ("C", C.c_int64), ("S", C.c_int64), ("workspace_triples", C.c_int64), ("y", vp), ("workspace", vp)]
+
+
+class BnApplyParams(C.Structure):
+    _fields_ = [("n", C.c_int64), ("C", C.c_int64), ("S", C.c_int64), ("workspace_triples", C.c_int64), ("eps", f32), ("momentum", f32), ("relu", i32),
+                ("reserved", i32), ("y", vp), ("workspace", vp), ("weight", vp), ("bias", vp), ("skip", vp), ("out", vp), ("saved_mean", vp),
+                ("saved_var", vp), ("running_mean", vp), ("running_var", vp), ("num_batches_tracked", vp)]
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -283,7 +293,8 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv2d_pack_params": Conv2dPackParams, "ucnerf_conv2d_params": Conv2dParams,
                  "ucnerf_maxpool2d_params": Maxpool2dParams, "ucnerf_lpips_layer_params": LpipsLayerParams,
                  "ucnerf_lpips_alex_params": LpipsAlexParams,
-                 "ucnerf_conv3d_pack_params": Conv3dPackParams, "ucnerf_conv3d_params": Conv3dParams}
+                 "ucnerf_conv3d_pack_params": Conv3dPackParams, "ucnerf_conv3d_params": Conv3dParams,
+                 "ucnerf_bn_stats_params": BnStatsParams, "ucnerf_bn_apply_params": BnApplyParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -370,6 +381,10 @@ SYMBOLS = {
     "ucnerf_conv3d_packed_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_conv3d_pack": (C.c_int, [_P, _P]),
     "ucnerf_conv3d": (C.c_int, [_P, _P]),
+    # batch-statistic batch-norm for the CNNs under train() + no_grad (additive to ABI v6)
+    "ucnerf_bn_partials": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ucnerf_bn_stats": (C.c_int, [_P, _P]),
+    "ucnerf_bn_apply": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

@@ -5,7 +5,9 @@ result keys; the cost-volume assembly (`homo_warp` + mask count + variance), the
 two stages (previous depth -> next stage's hypothesis volume) run as the HIP kernels `ucnerf_cost_volume` /
 `ucnerf_depth_regress` / `ucnerf_depth_hypotheses`.  The CNNs -- the feature pyramid `FeatureNet` (:309-410) and the 3-D
 regularisation network `CostRegNet` (:412-443) -- are mirrored here with the reference's parameter names: they train through torch's
-layers and, under eval() + no_grad, run on `ucnerf_conv2d_bias_relu` / `ucnerf_conv3d` with the batch-norms folded into the weights.
+layers and, under eval() + no_grad, run on `ucnerf_conv2d_bias_relu` / `ucnerf_conv3d` with the batch-norms folded into the weights.  Under
+train() + no_grad -- how the reference's validation_step runs them (train.py:226-243) -- batch_stats="device" keeps the convolutions on those
+kernels and normalises with the statistics of the batch itself on `ucnerf_bn_stats` / `ucnerf_bn_apply`, moving the running statistics as torch does.
 `CascadeMVSNet(...)` still takes the caller's modules; `CascadeMVSNet.with_cnns(...)` builds its own.
 
 The cost volume and the regression have backward kernels behind `torch.autograd.Function`s, so the feature network
@@ -25,6 +27,7 @@ from .. import ops
 
 
 INFERENCE_ROUTES = ("device", "torch")
+BATCH_STATS_ROUTES = ("torch", "device")
 
 
 class Conv2d(nn.Module):
@@ -106,15 +109,17 @@ class _InferenceCache:
     it was made from, at the version and on the device it had then.  The cache keeps the tensors themselves: an object it holds cannot be
     freed and its address reused by another, so identity is a sound test (an address is not: README, round 5)."""
 
-    def __init__(self):
+    def __init__(self, watch=None):
+        """`watch`: module -> the tensors the cached value was made from; every parameter and buffer without it."""
         self.sources, self.stamps, self.value = None, None, None
+        self.watch = watch if watch is not None else (lambda module: list(module.parameters()) + list(module.buffers()))
 
     @staticmethod
     def _stamp(t):
         return (t._version, t.device, t.dtype)
 
     def get(self, module, build):
-        now = list(module.parameters()) + list(module.buffers())
+        now = self.watch(module)
         if (self.sources is None or len(now) != len(self.sources)
                 or any(a is not b or self._stamp(a) != s for a, b, s in zip(now, self.sources, self.stamps))):
             self.value = build()
@@ -128,23 +133,53 @@ def _check_route(inference):
     return inference
 
 
+def _check_batch_stats(batch_stats):
+    if batch_stats not in BATCH_STATS_ROUTES:
+        raise ValueError("uc_nerf_amd: batch_stats=%r -- \"torch\" (torch's layers in training mode) or \"device\" (the HIP kernels under "
+                         "train() + no_grad, with inference=\"device\")" % (batch_stats,))
+    return batch_stats
+
+
 def _device_route(module, x):
     return module.inference == "device" and not module.training and not torch.is_grad_enabled() and x.is_cuda
+
+
+def _batch_stats_route(module, x):
+    """train() + no_grad on the device with batch_stats="device", every batch-norm keeping running statistics with a float momentum."""
+    if not (module.inference == "device" and module.batch_stats == "device" and module.training and not torch.is_grad_enabled() and x.is_cuda):
+        return False
+    return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
+               for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
+
+
+def _conv_weights(module):
+    """What the raw packed weights of the batch-statistic route were made from: the convolutions' weights, not the buffers every call moves."""
+    return [m.weight for m in module.modules() if isinstance(m, (nn.Conv2d, nn.Conv3d, nn.ConvTranspose3d))]
+
+
+def _bn_train(layer, y, skip=None):
+    """The layer's batch-norm, ReLU and skip addition in place on its convolution's output, with the batch's own statistics."""
+    bn = layer.bn
+    return ops.batch_norm_train(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum=bn.momentum, eps=bn.eps,
+                                relu=layer.relu, skip=skip, out=y)
 
 
 class FeatureNet(nn.Module):
     """mvs_models.py:309-410, the "fpn" pyramid with three stages: image [n,3,H,W] -> {"stage1": [n,4c,H/4,W/4], "stage2": [n,2c,H/2,W/2],
     "stage3": [n,c,H,W]}.  Parameter and buffer names are the reference's, so a checkpoint's `feature.*` keys load strictly.
     Two routes: torch's layers whenever grad is enabled, the module is in training mode or the input is not on a ROCm device; with
-    inference="device", under eval() + no_grad, `ops.conv2d_bias_relu` with the batch-norms folded into weights and biases (packed once, cached)."""
+    inference="device", under eval() + no_grad, `ops.conv2d_bias_relu` with the batch-norms folded into weights and biases (packed once, cached).
+    batch_stats="device" adds a third, under train() + no_grad: the same convolution launches with the raw weights, each batch-normed layer
+    followed by `ops.batch_norm_train` in place (batch statistics, the running statistics moved as torch moves them)."""
 
-    def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device"):
+    def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device", batch_stats="torch"):
         super().__init__()
         if arch_mode != "fpn" or num_stage != 3:
             raise NotImplementedError("uc_nerf_amd FeatureNet: arch_mode=%r num_stage=%r -- only arch_mode=\"fpn\" with num_stage=3 is built"
                                       % (arch_mode, num_stage))
         self.arch_mode, self.stride, self.base_channels, self.num_stage = arch_mode, stride, base_channels, num_stage
         self.inference = _check_route(inference)
+        self.batch_stats = _check_batch_stats(batch_stats)
         c = base_channels
         self.conv0 = nn.Sequential(Conv2d(3, c, 3, 1, padding=1), Conv2d(c, c, 3, 1, padding=1))
         self.conv1 = nn.Sequential(Conv2d(c, 2 * c, 5, stride=2, padding=2), Conv2d(2 * c, 2 * c, 3, 1, padding=1), Conv2d(2 * c, 2 * c, 3, 1, padding=1))
@@ -156,6 +191,7 @@ class FeatureNet(nn.Module):
         self.out3 = nn.Conv2d(4 * c, c, 3, padding=1, bias=False)
         self.out_channels = [4 * c, 2 * c, c]
         self._cache = _InferenceCache()
+        self._raw_cache = _InferenceCache(_conv_weights)
 
     def _layers(self):
         return list(self.conv0) + list(self.conv1) + list(self.conv2) + [self.out1, self.inner1, self.inner2, self.out2, self.out3]
@@ -167,9 +203,18 @@ class FeatureNet(nn.Module):
             out.append((ops.conv2d_pack(w.float()), b.float().contiguous()))
         return out
 
+    def _raw(self):
+        out = []
+        for layer in self._layers():
+            conv = layer.conv if hasattr(layer, "conv") else layer
+            out.append((ops.conv2d_pack(conv.weight.detach().float()), torch.zeros(conv.out_channels, device=conv.weight.device)))
+        return out
+
     def forward(self, x):
         if _device_route(self, x):
             return self._forward_device(x)
+        if _batch_stats_route(self, x):
+            return self._forward_device(x, batch_stats=True)
         conv0 = self.conv0(x)
         conv1 = self.conv1(conv0)
         conv2 = self.conv2(conv1)
@@ -180,16 +225,22 @@ class FeatureNet(nn.Module):
         outputs["stage3"] = self.out3(intra)
         return outputs
 
-    def _forward_device(self, x):
+    def _forward_device(self, x, batch_stats=False):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
             raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
                                "it), got %s" % (tuple(x.shape),))
-        folded = self._cache.get(self, self._fold)
+        folded = self._raw_cache.get(self, self._raw) if batch_stats else self._cache.get(self, self._fold)
         layers = self._layers()
 
         def run(i, t, relu):
             conv = layers[i].conv if hasattr(layers[i], "conv") else layers[i]
-            return ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=relu)
+            if not batch_stats:
+                return ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=relu)
+            if conv is layers[i]:                            # no batch-norm: the convolution with its own bias, as above
+                bias = conv.bias.detach() if conv.bias is not None else folded[i][1]
+                return ops.conv2d_bias_relu(t, folded[i][0], bias, stride=conv.stride[0], pad=conv.padding[0], relu=relu)
+            y = ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=False)
+            return _bn_train(layers[i], y)
 
         conv0 = run(1, run(0, x, True), True)
         conv1 = run(4, run(3, run(2, conv0, True), True), True)
@@ -210,9 +261,10 @@ class CostRegNet(nn.Module):
 
     ORDER = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11", "prob")
 
-    def __init__(self, in_channels, base_channels, inference="device"):
+    def __init__(self, in_channels, base_channels, inference="device", batch_stats="torch"):
         super().__init__()
         self.inference = _check_route(inference)
+        self.batch_stats = _check_batch_stats(batch_stats)
         c = base_channels
         self.conv0 = Conv3d(in_channels, c, padding=1)
         self.conv1 = Conv3d(c, 2 * c, stride=2, padding=1)
@@ -226,6 +278,7 @@ class CostRegNet(nn.Module):
         self.conv11 = Deconv3d(2 * c, c, stride=2, padding=1, output_padding=1)
         self.prob = nn.Conv3d(c, 1, 3, stride=1, padding=1, bias=False)
         self._cache = _InferenceCache()
+        self._raw_cache = _InferenceCache(_conv_weights)
 
     def _fold(self):
         out = {}
@@ -235,9 +288,21 @@ class CostRegNet(nn.Module):
             out[name] = (ops.conv3d_pack(w.float(), transposed=getattr(layer, "transposed", False)), b.float().contiguous())
         return out
 
+    def _raw(self):
+        out = {}
+        for name in self.ORDER:
+            layer = getattr(self, name)
+            conv = layer.conv if hasattr(layer, "conv") else layer
+            cout = conv.out_channels
+            out[name] = (ops.conv3d_pack(conv.weight.detach().float(), transposed=getattr(layer, "transposed", False)),
+                         torch.zeros(cout, device=conv.weight.device))
+        return out
+
     def forward(self, x):
         if _device_route(self, x):
             return self._forward_device(x)
+        if _batch_stats_route(self, x):
+            return self._forward_device(x, batch_stats=True)
         conv0 = self.conv0(x)
         conv2 = self.conv2(self.conv1(conv0))
         conv4 = self.conv4(self.conv3(conv2))
@@ -247,14 +312,18 @@ class CostRegNet(nn.Module):
         cost = conv0 + self.conv11(x)
         return cost, self.prob(cost)
 
-    def _forward_device(self, x):
+    def _forward_device(self, x, batch_stats=False):
         if x.dim() != 5 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
             raise RuntimeError("uc_nerf_amd CostRegNet: the device route takes [n,C,D,H,W] with D, H and W divisible by 8 (three halvings, three "
                                "doublings and the skip additions between them), got %s" % (tuple(x.shape),))
-        f = self._cache.get(self, self._fold)
+        f = self._raw_cache.get(self, self._raw) if batch_stats else self._cache.get(self, self._fold)
 
         def conv(name, t, stride=1, skip=None, relu=True):
-            return ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=relu, skip=skip, transposed=f[name][0].transposed)
+            layer = getattr(self, name)
+            if not batch_stats or getattr(layer, "bn", None) is None:
+                return ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=relu, skip=skip, transposed=f[name][0].transposed)
+            y = ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=False, skip=None, transposed=f[name][0].transposed)
+            return _bn_train(layer, y, skip)
 
         conv0 = conv("conv0", x)
         conv2 = conv("conv2", conv("conv1", conv0, 2))
@@ -378,14 +447,15 @@ class CascadeMVSNet(nn.Module):
 
     @classmethod
     def with_cnns(cls, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
-                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device"):
+                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch"):
         """The net with its own `FeatureNet` and one `CostRegNet` per stage (mvs_models.py:678-687), so that a reference checkpoint loads and
-        runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch")."""
+        runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch");
+        `batch_stats`: the one they take under train() + no_grad ("torch", or "device" with inference="device")."""
         if share_cr:
             raise NotImplementedError("uc_nerf_amd CascadeMVSNet.with_cnns: share_cr=True (one regulariser for stages whose feature channels "
                                       "differ; the reference's constructor fails on it too) -- hand a module in through CascadeMVSNet(...)")
-        feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference)
-        regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference)
+        feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference, batch_stats=batch_stats)
+        regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference, batch_stats=batch_stats)
                               for i in range(len(ndepths))])
         return cls(view_num, ndepths, depth_interals_ratio, share_cr, grad_method, arch_mode, cr_base_chs, feature=feature, cost_regularization=regs)
 

@@ -1,4 +1,4 @@
-"""The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip)."""
+"""The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip) and the batch-statistic batch-norm of both CNNs (csrc/bn.hip)."""
 import torch
 
 from .. import _lib as L
@@ -68,3 +68,58 @@ def conv3d(x, weight, bias, stride=1, pad=0, relu=True, skip=None, transposed=Fa
     p.x, p.packed, p.bias, p.skip, p.y = _ptr(x), _ptr(w.packed), _ptr(bias), _ptr(skip), _ptr(y)
     _launch("ucnerf_conv3d", p, x.device)
     return y
+
+
+def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, relu=True, skip=None, out=None,
+                     return_stats=False):
+    """Train-mode batch-norm of y [n,C,*spatial] (float32, contiguous, on the device) with the statistics of the batch itself, forward only
+    (csrc/bn.hip: `ucnerf_bn_stats` then `ucnerf_bn_apply`, the order of every sum fixed, nothing read back): out = act((y - mean) / sqrt(var +
+    eps) * weight + bias) (+ skip), var the biased variance, act ReLU with `relu`, `skip` added AFTER the activation.  `running_mean`,
+    `running_var` (float32 [C]) and `num_batches_tracked` (one int64) move in place as nn.BatchNorm moves them (the unbiased variance, momentum a
+    float in (0, 1]); their version counters are bumped, since the kernels write through raw pointers.  `out`: a tensor like y to write into, y
+    itself for in place.  -> out, or (out, saved_mean, saved_var) with `return_stats`.  No autograd: inputs that require grad are used detached."""
+    if torch.is_tensor(y) and y.dim() >= 2 and 0 < y.numel() == y.shape[1]:     # n S == 1: torch's own refusal, before anything else is looked at
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(y.size()))
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.dim() >= 2 and y.is_contiguous() and y.numel() > 0):
+        raise RuntimeError("uc_nerf_amd.batch_norm_train: y must be a non-empty contiguous float32 [n,C,*spatial] tensor on a ROCm device, got %s"
+                           % ("%s %s on %s" % (tuple(y.shape), y.dtype, y.device) if torch.is_tensor(y) else type(y)))
+    given, y = out, y.detach()
+    n, C = y.shape[0], y.shape[1]
+    S = y.numel() // (n * C)
+    if momentum is None or not 0.0 < float(momentum) <= 1.0 or not float(eps) > 0.0:
+        raise RuntimeError("uc_nerf_amd.batch_norm_train: momentum=%r eps=%r (a float momentum in (0, 1], a positive eps)" % (momentum, eps))
+    per_channel = []
+    for t, name in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == (C,) and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.batch_norm_train: %s must be a contiguous float32 [%d] tensor on y's device" % (name, C))
+        per_channel.append(t.detach())
+    weight, bias = per_channel[0], per_channel[1]
+    nbt = num_batches_tracked
+    if not (torch.is_tensor(nbt) and nbt.dtype == torch.int64 and nbt.numel() == 1 and nbt.device == y.device):
+        raise RuntimeError("uc_nerf_amd.batch_norm_train: num_batches_tracked must be one int64 element on y's device")
+    for t, name in ((skip, "skip"), (out, "out")):
+        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == y.device and t.shape == y.shape and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.batch_norm_train: %s must be a contiguous float32 tensor of y's shape %s on its device" % (name, tuple(y.shape)))
+    if skip is not None:
+        skip = skip.detach()
+    out = torch.empty_like(y) if out is None else out.detach()
+    P = L.lib().ucnerf_bn_partials(n, S)
+    if P < 0:
+        raise RuntimeError("uc_nerf_amd.batch_norm_train: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
+                           % (tuple(y.shape),))
+    workspace = torch.empty((C, P, 3), dtype=torch.float64, device=y.device)
+    saved = torch.empty((2, C), device=y.device)
+    s = L.BnStatsParams()
+    s.n, s.C, s.S, s.workspace_triples, s.y, s.workspace = n, C, S, C * P, _ptr(y), _ptr(workspace)
+    _launch("ucnerf_bn_stats", s, y.device)
+    a = L.BnApplyParams()
+    a.n, a.C, a.S, a.workspace_triples, a.eps, a.momentum, a.relu = n, C, S, C * P, float(eps), float(momentum), int(bool(relu))
+    a.y, a.workspace, a.weight, a.bias, a.skip, a.out = _ptr(y), _ptr(workspace), _ptr(weight), _ptr(bias), _ptr(skip), _ptr(out)
+    a.saved_mean, a.saved_var, a.running_mean, a.running_var = _ptr(saved[0]), _ptr(saved[1]), _ptr(running_mean), _ptr(running_var)
+    a.num_batches_tracked = _ptr(nbt)
+    _launch("ucnerf_bn_apply", a, y.device)
+    for t in (running_mean, running_var, nbt):
+        torch.autograd.graph.increment_version(t)
+    if given is not None:
+        out = given                                        # the caller's own tensor (y itself for in place), not the detached alias
+    return (out, saved[0], saved[1]) if return_stats else out
