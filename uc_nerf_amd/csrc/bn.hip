@@ -129,7 +129,9 @@ __global__ __launch_bounds__(BN_APPLY_THREADS) void bn_apply_kernel(ApplyArgs a,
     Triple all = {tr[0][0], tr[0][1], tr[0][2]};
     for (int j = 1; j < a.P; ++j) all = chan(all, Triple{tr[j][0], tr[j][1], tr[j][2]});        // every thread, the same operations
     const float mu = (float)all.mean, var = (float)(all.m2 / all.n);
-    const float s = __fdiv_rn(a.gamma[c], __fsqrt_rn(var + a.eps)), beta = a.beta[c];
+    // IEEE square root and division: plain sqrtf and / under the build's -fhip-fp32-correctly-rounded-divide-sqrt.  (__fsqrt_rn is NOT that here:
+    // without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define it as the native v_sqrt_f32, one float32 spacing off for some arguments.)
+    const float s = a.gamma[c] / sqrtf(var + a.eps), beta = a.beta[c];
     if (blockIdx.x == 0 && t == 0) {
         const float m = a.momentum, unbiased = (float)(all.m2 / (all.n - 1.0));
         a.saved_mean[c] = mu;
