@@ -1024,6 +1024,96 @@ struct ucnerf_bn_apply_params {
 typedef struct ucnerf_bn_apply_params ucnerf_bn_apply_params;
 int ucnerf_bn_apply(const ucnerf_bn_apply_params* p, void* stream);
 
+/* Training CostRegNet on the device: the weight gradient of ucnerf_conv3d and the backward of the batch-statistic batch-norm with its ReLU.
+ * (Added to ABI v6; nothing above moved.)  The INPUT gradient of a convolution needs no entry point of its own: it is ucnerf_conv3d on
+ * grad_y with the weight presented the other way round (uc_nerf_amd.ops.conv3d_dgrad).
+ *
+ * ucnerf_conv3d_wgrad: grad_weight of one layer, K = 3 only (K = 1 is refused with UCNERF_EINVAL), float32, NCDHW contiguous.  D, H, W are the
+ *   sizes of the layer's INPUT x in both forms.  Both forms are one computation over a small grid s = (sd, sh, sw) and a big one,
+ *   out[a][b][t] = sum over (img, s) of A[img,a,s] B[img,b, stride s - pad + t], t = (td, th, tw) = the flat tap 9 td + 3 th + tw, a tap outside
+ *   the big grid contributing +0:
+ *     transposed == 0 (stride 1 or 2, 0 <= pad <= 64, weight [cout,cin,3,3,3]): A = grad_y [n,cout,OD,OH,OW], O = (I + 2 pad - 3) / stride + 1,
+ *       B = x [n,cin,D,H,W]; grad_weight [cout,cin,27].
+ *     transposed == 1 (stride 2, pad 1, output_padding 1, weight [cin,cout,3,3,3]): A = x [n,cin,D,H,W], B = grad_y [n,cout,2D,2H,2W];
+ *       grad_weight [cin,cout,27].
+ *   Exact fp32 products and fp32 accumulation on v_mfma_f32_16x16x4_f32 for every shape (a side with one channel is padded to a 16-row tile
+ *   like any other), both operands staged through LDS 32 voxels at a time.  The voxels v = img S + s (S = the small grid's size, V = n S of
+ *   them) are the reduction dimension and are cut into chunks; no atomics, every store a plain vector store, two calls give the same bits.
+ *   SUMMATION ORDER (fixed, part of the interface).  Ca, Cb = the channels of A and B; tiles = ceil(Ca / 16) ceil(Cb / 16);
+ *     C0 = min(ceil(V / 32), max(1, ceil(512 / tiles))); the chunk length L = 32 ceil(V / (32 C0)); chunks = ceil(V / L); chunk c is the voxels
+ *     [c L, min((c + 1) L, V)).  Within a chunk P_c = one fmaf chain from +0 over ascending v (the MFMA adds four consecutive voxels per
+ *     instruction, the lowest first; a tap outside the big grid enters as the product a * +0).  grad_weight = (((+0 + P_0) + P_1) + ...) over
+ *     ascending c, by a second launch.
+ *   workspace: ucnerf_conv3d_wgrad_workspace_floats(...) = chunks Ca Cb 27 floats, laid out [chunk][a][t][b], every element overwritten; < 0 on a
+ *     bad argument; pure host.  Limits: cin, cout <= 2^16; Ca S, Cb big < 2^31 per image; V < 2^31 - 1024; cin cout 27 < 2^31.
+ *   UCNERF_EINVAL before any device call: NULL params or array, negative n, non-positive cin / cout / D / H / W, K != 3, a stride / pad /
+ *     transposed combination outside the above, workspace_floats that does not match the query.  n == 0 is success, nothing launched.
+ *
+ * ucnerf_bn_bwd_reduce then ucnerf_bn_bwd_apply: the backward of ucnerf_bn_stats / ucnerf_bn_apply (with the ReLU, without the skip: the skip's
+ *   gradient is g itself).  g = the gradient of the layer's output, y = the convolution's raw output the forward normalised, saved_mean = mu
+ *   and saved_var = sigma^2 as the forward wrote them.  The same slices as the forward (P = ucnerf_bn_partials(n, S)), a float64 workspace
+ *   [C, P, 2], no atomics, nothing read back, two calls give the same bits.
+ *   Per element, in float32: s = weight[c] / sqrt(sigma^2 + eps) and z = fma(y - mu, s, bias[c]), the very expressions of ucnerf_bn_apply (IEEE
+ *   division and square root), so z is the forward's pre-activation value bit for bit; the mask m = relu ? !(z <= 0) : 1 (torch's threshold
+ *   rule: a NaN passes); gm = m ? g : 0.  Everything after that is FLOAT64 per element, the values converted exactly, separate multiplications
+ *   and additions, and rounded once to float32 at the store.
+ *   reduce: workspace[(c P + j) 2 + 0 .. 1] = (A_j, B_j) = (sum gm, sum gm (y - mu)) over slice j.  Order: thread t of 1024 adds its values in
+ *     the order the forward's thread walks them (chunk k, quads (4 k + u) 1024 + t, ascending i), from 0; lanes: for d = 1, 2, .. 32 lane
+ *     l < 64 - d adds lane l + d's value of before the step; waves: ((wave 0 + wave 1) + ...) ascending.
+ *   apply: every block folds A = ((A_0 + A_1) + ...), B likewise, ascending; r = 1 / sqrt(sigma^2 + eps), k1 = A / N, k2 = r r B / N,
+ *     sg = weight[c] r, all float64; grad_y = sg ((gm - k1) - (y - mu) k2); one block per channel writes grad_bias[c] = A and
+ *     grad_weight[c] = B r, each rounded once.  grad_y may be g itself (not a shifted overlap).
+ *   Both are memory-bound: reduce reads |g| + |y|, apply reads them again and writes |y|.
+ *   UCNERF_EINVAL before any device call: as ucnerf_bn_stats (shape, limits, alignment), NULL arrays, eps <= 0, workspace_pairs < C P. */
+struct ucnerf_conv3d_wgrad_params {
+    int32_t n, cin, D, H, W, cout, K, stride, pad;   /* of the layer: x is [n,cin,D,H,W] */
+    int32_t transposed;
+    int64_t workspace_floats;  /* floats `workspace` holds = ucnerf_conv3d_wgrad_workspace_floats(the same arguments) */
+    const float* x;            /* [n,cin,D,H,W] */
+    const float* grad_y;       /* the layer output's gradient: [n,cout,OD,OH,OW], transposed [n,cout,2D,2H,2W] */
+    float* workspace;          /* overwritten */
+    float* grad_weight;        /* [cout,cin,3,3,3], transposed [cin,cout,3,3,3], overwritten */
+};
+typedef struct ucnerf_conv3d_wgrad_params ucnerf_conv3d_wgrad_params;
+int64_t ucnerf_conv3d_wgrad_workspace_floats(int32_t n, int32_t cin, int32_t cout, int32_t D, int32_t H, int32_t W, int32_t K, int32_t stride, int32_t pad,
+                                             int32_t transposed);
+int ucnerf_conv3d_wgrad(const ucnerf_conv3d_wgrad_params* p, void* stream);
+
+struct ucnerf_bn_bwd_reduce_params {
+    int64_t n, C, S;
+    int64_t workspace_pairs;   /* pairs (2 float64 each) the workspace holds, at least C P */
+    float eps;
+    int32_t relu;              /* 1: the forward applied max(., 0) */
+    const float* g;            /* [n,C,S] */
+    const float* y;            /* [n,C,S], the forward's input */
+    const float* saved_mean;   /* [C] */
+    const float* saved_var;    /* [C] */
+    const float* weight;       /* gamma [C] */
+    const float* bias;         /* beta [C] */
+    double* workspace;         /* [C,P,2], overwritten */
+};
+typedef struct ucnerf_bn_bwd_reduce_params ucnerf_bn_bwd_reduce_params;
+int ucnerf_bn_bwd_reduce(const ucnerf_bn_bwd_reduce_params* p, void* stream);
+
+struct ucnerf_bn_bwd_apply_params {
+    int64_t n, C, S;
+    int64_t workspace_pairs;
+    float eps;
+    int32_t relu;
+    const float* g;
+    const float* y;
+    const float* saved_mean;
+    const float* saved_var;
+    const float* weight;
+    const float* bias;
+    const double* workspace;   /* as ucnerf_bn_bwd_reduce wrote it for the same arguments */
+    float* grad_y;             /* [n,C,S]; may be g */
+    float* grad_weight;        /* [C], overwritten */
+    float* grad_bias;          /* [C], overwritten */
+};
+typedef struct ucnerf_bn_bwd_apply_params ucnerf_bn_bwd_apply_params;
+int ucnerf_bn_bwd_apply(const ucnerf_bn_bwd_apply_params* p, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * e2   a whole validation image on the device -- train.py:274-288 (the reference pulls every rendered chunk to the host, concatenates, clamps and
  *      permutes there) and utils/utils.py:58-77 (visualize_depth: numpy normalisation, cv2.applyColorMap, PIL, ToTensor).  Here a chunk is

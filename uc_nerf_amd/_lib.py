@@ -224,6 +224,22 @@ class BnApplyParams(C.Structure):
                 ("saved_var", vp), ("running_mean", vp), ("running_var", vp), ("num_batches_tracked", vp)]
 
 
+class Conv3dWgradParams(C.Structure):
+    _fields_ = [("n", i32), ("cin", i32), ("D", i32), ("H", i32), ("W", i32), ("cout", i32), ("K", i32), ("stride", i32), ("pad", i32),
+                ("transposed", i32), ("workspace_floats", C.c_int64), ("x", vp), ("grad_y", vp), ("workspace", vp), ("grad_weight", vp)]
+
+
+class BnBwdReduceParams(C.Structure):
+    _fields_ = [("n", C.c_int64), ("C", C.c_int64), ("S", C.c_int64), ("workspace_pairs", C.c_int64), ("eps", f32), ("relu", i32), ("g", vp),
+                ("y", vp), ("saved_mean", vp), ("saved_var", vp), ("weight", vp), ("bias", vp), ("workspace", vp)]
+
+
+class BnBwdApplyParams(C.Structure):
+    _fields_ = [("n", C.c_int64), ("C", C.c_int64), ("S", C.c_int64), ("workspace_pairs", C.c_int64), ("eps", f32), ("relu", i32), ("g", vp),
+                ("y", vp), ("saved_mean", vp), ("saved_var", vp), ("weight", vp), ("bias", vp), ("workspace", vp), ("grad_y", vp),
+                ("grad_weight", vp), ("grad_bias", vp)]
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -294,7 +310,9 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_maxpool2d_params": Maxpool2dParams, "ucnerf_lpips_layer_params": LpipsLayerParams,
                  "ucnerf_lpips_alex_params": LpipsAlexParams,
                  "ucnerf_conv3d_pack_params": Conv3dPackParams, "ucnerf_conv3d_params": Conv3dParams,
-                 "ucnerf_bn_stats_params": BnStatsParams, "ucnerf_bn_apply_params": BnApplyParams}
+                 "ucnerf_bn_stats_params": BnStatsParams, "ucnerf_bn_apply_params": BnApplyParams,
+                 "ucnerf_conv3d_wgrad_params": Conv3dWgradParams, "ucnerf_bn_bwd_reduce_params": BnBwdReduceParams,
+                 "ucnerf_bn_bwd_apply_params": BnBwdApplyParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -385,6 +403,11 @@ SYMBOLS = {
     "ucnerf_bn_partials": (C.c_int64, [C.c_int64, C.c_int64]),
     "ucnerf_bn_stats": (C.c_int, [_P, _P]),
     "ucnerf_bn_apply": (C.c_int, [_P, _P]),
+    # CostRegNet's training route: the convolution's weight gradient and the batch-norm backward (additive to ABI v6)
+    "ucnerf_conv3d_wgrad_workspace_floats": (C.c_int64, [C.c_int32] * 10),
+    "ucnerf_conv3d_wgrad": (C.c_int, [_P, _P]),
+    "ucnerf_bn_bwd_reduce": (C.c_int, [_P, _P]),
+    "ucnerf_bn_bwd_apply": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

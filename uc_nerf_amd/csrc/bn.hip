@@ -112,6 +112,12 @@ __global__ __launch_bounds__(BN_STATS_THREADS) void bn_stats_kernel(const float*
     }
 }
 
+// The scale and the pre-activation value as the forward's apply forms them; the backward kernels below recompute both through these same
+// expressions (IEEE square root and division: plain sqrtf and / under the build's -fhip-fp32-correctly-rounded-divide-sqrt.  __fsqrt_rn is NOT
+// that here: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define it as the native v_sqrt_f32, one float32 spacing off for some arguments).
+__device__ __forceinline__ float bn_scale(float gamma, float var, float eps) { return gamma / sqrtf(var + eps); }
+__device__ __forceinline__ float bn_affine(float v, float mu, float s, float beta) { return fmaf(v - mu, s, beta); }
+
 struct ApplyArgs {
     const float *y, *skip, *gamma, *beta;
     float *out, *saved_mean, *saved_var, *running_mean, *running_var;
@@ -129,9 +135,7 @@ __global__ __launch_bounds__(BN_APPLY_THREADS) void bn_apply_kernel(ApplyArgs a,
     Triple all = {tr[0][0], tr[0][1], tr[0][2]};
     for (int j = 1; j < a.P; ++j) all = chan(all, Triple{tr[j][0], tr[j][1], tr[j][2]});        // every thread, the same operations
     const float mu = (float)all.mean, var = (float)(all.m2 / all.n);
-    // IEEE square root and division: plain sqrtf and / under the build's -fhip-fp32-correctly-rounded-divide-sqrt.  (__fsqrt_rn is NOT that here:
-    // without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define it as the native v_sqrt_f32, one float32 spacing off for some arguments.)
-    const float s = a.gamma[c] / sqrtf(var + a.eps), beta = a.beta[c];
+    const float s = bn_scale(a.gamma[c], var, a.eps), beta = a.beta[c];
     if (blockIdx.x == 0 && t == 0) {
         const float m = a.momentum, unbiased = (float)(all.m2 / (all.n - 1.0));
         a.saved_mean[c] = mu;
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(BN_APPLY_THREADS) void bn_apply_kernel(ApplyArgs a,
         if (a.skip) bn_load_quad(a.skip, w, c, i, w.N, sk);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float r = fmaf(v[e] - mu, s, beta);
+            float r = bn_affine(v[e], mu, s, beta);
             if (a.relu) r = r < 0.f ? 0.f : r;             // (a NaN stays)
             v[e] = a.skip ? r + sk[e] : r;
         }
@@ -160,6 +164,95 @@ __global__ __launch_bounds__(BN_APPLY_THREADS) void bn_apply_kernel(ApplyArgs a,
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 if (i + e < w.N) a.out[bn_addr(w, c, i + e)] = v[e];
+        }
+    }
+}
+
+// ---- backward (ucnerf_bn_bwd_reduce, ucnerf_bn_bwd_apply): the same slices and quads as the forward pair, a float64 workspace [C, P, 2].
+// gm = g where the forward's ReLU let the value through (z = bn_affine(y, mu, s, beta), the mask is !(z <= 0): torch's threshold rule), else 0.
+struct BwdArgs {
+    const float *g, *y, *mean, *var, *gamma, *beta;
+    float eps;
+    int relu, P;
+};
+
+__device__ __forceinline__ float bn_masked(const BwdArgs& a, float g, float y, float mu, float s, float beta) {
+    return (!a.relu || !(bn_affine(y, mu, s, beta) <= 0.f)) ? g : 0.f;
+}
+
+__global__ __launch_bounds__(BN_STATS_THREADS) void bn_bwd_reduce_kernel(BwdArgs a, Walk w, unsigned L, double* __restrict__ ws) {
+    const int j = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+    const unsigned begin = (unsigned)j * L;
+    const unsigned end = min(begin + L, w.N);
+    const float mu = a.mean[c], beta = a.beta[c], s = bn_scale(a.gamma[c], a.var[c], a.eps);
+    double sa = 0.0, sb = 0.0;
+    for (unsigned q0 = 0; begin + q0 * 4u < end; q0 += BN_CHUNK_QUADS * BN_STATS_THREADS) {
+        float gv[BN_CHUNK_QUADS][4], yv[BN_CHUNK_QUADS][4];
+        unsigned at[BN_CHUNK_QUADS];
+#pragma unroll
+        for (int u = 0; u < BN_CHUNK_QUADS; ++u) {
+            at[u] = begin + (q0 + (unsigned)u * BN_STATS_THREADS + (unsigned)t) * 4u;
+            if (at[u] < end) { bn_load_quad(a.g, w, c, at[u], end, gv[u]); bn_load_quad(a.y, w, c, at[u], end, yv[u]); }
+        }
+#pragma unroll
+        for (int u = 0; u < BN_CHUNK_QUADS; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (at[u] < end && at[u] + e < end) {
+                    const double gm = (double)bn_masked(a, gv[u][e], yv[u][e], mu, s, beta);
+                    sa += gm;
+                    sb += gm * ((double)yv[u][e] - (double)mu);
+                }
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double oa = __shfl_down(sa, d), ob = __shfl_down(sb, d);
+        if ((t & 63) + d < 64) { sa += oa; sb += ob; }
+    }
+    __shared__ double waves[BN_STATS_THREADS / 64][2];
+    if ((t & 63) == 0) { waves[t >> 6][0] = sa; waves[t >> 6][1] = sb; }
+    __syncthreads();
+    if (t == 0) {
+        for (int wv = 1; wv < BN_STATS_THREADS / 64; ++wv) { sa += waves[wv][0]; sb += waves[wv][1]; }
+        double* o = ws + ((size_t)c * (size_t)a.P + (size_t)j) * 2;
+        o[0] = sa; o[1] = sb;
+    }
+}
+
+__global__ __launch_bounds__(BN_APPLY_THREADS) void bn_bwd_apply_kernel(BwdArgs a, Walk w, const double* __restrict__ ws, float* dy, float* __restrict__ dgamma,
+                                                                        float* __restrict__ dbeta) {
+    const int c = blockIdx.y, t = threadIdx.x;
+    __shared__ double pr[BN_MAX_PARTIALS][2];
+    if (t < a.P * 2) pr[t / 2][t % 2] = ws[(size_t)c * (size_t)a.P * 2 + t];
+    __syncthreads();
+    double A = pr[0][0], B = pr[0][1];
+    for (int j = 1; j < a.P; ++j) { A += pr[j][0]; B += pr[j][1]; }                              // every thread, the same operations
+    const float mu = a.mean[c], beta = a.beta[c], var = a.var[c], s = bn_scale(a.gamma[c], var, a.eps);
+    const double r = 1.0 / sqrt((double)var + (double)a.eps), N = (double)w.N;
+    const double k1 = A / N, k2 = r * r * B / N, sg = (double)a.gamma[c] * r;
+    if (blockIdx.x == 0 && t == 0) {
+        dbeta[c] = (float)A;
+        dgamma[c] = (float)(B * r);
+    }
+    const unsigned base = blockIdx.x * (unsigned)BN_APPLY_CHUNK;
+#pragma unroll
+    for (int k = 0; k < BN_APPLY_QUADS; ++k) {
+        const unsigned i = base + ((unsigned)k * BN_APPLY_THREADS + (unsigned)t) * 4u;
+        if (i >= w.N) break;
+        float gv[4], yv[4];
+        bn_load_quad(a.g, w, c, i, w.N, gv);
+        bn_load_quad(a.y, w, c, i, w.N, yv);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const double gm = (double)bn_masked(a, gv[e], yv[e], mu, s, beta);
+            gv[e] = (float)(sg * ((gm - k1) - ((double)yv[e] - (double)mu) * k2));
+        }
+        if (w.vec) {
+            *reinterpret_cast<float4*>(dy + bn_addr(w, c, i)) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i + e < w.N) dy[bn_addr(w, c, i + e)] = gv[e];
         }
     }
 }
@@ -230,6 +323,47 @@ int ucnerf_bn_apply(const ucnerf_bn_apply_params* p, void* stream) {
     a.ws = p->workspace; a.eps = p->eps; a.momentum = p->momentum; a.P = (int)P; a.relu = p->relu != 0;
     hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((N + BN_APPLY_CHUNK - 1) / BN_APPLY_CHUNK), (unsigned)p->C), dim3(BN_APPLY_THREADS), 0, (hipStream_t)stream, a, w);
     return check_launch("bn_apply");
+}
+
+static int bn_bwd_common(const char* who, int64_t n, int64_t C, int64_t S, int64_t pairs, float eps, const void* g, const void* y, const void* mean, const void* var,
+                         const void* gamma, const void* beta, const void* ws, int64_t* N, int64_t* P) {
+    if (int rc = bn_shape(who, n, C, S, N)) return rc;
+    UCNERF_REQUIRE(g && y && mean && var && gamma && beta && ws, "%s: null g, y, saved_mean, saved_var, weight, bias or workspace", who);
+    UCNERF_REQUIRE(eps > 0.f, "%s: eps=%g (must be positive)", who, (double)eps);
+    *P = bn_partials(*N);
+    UCNERF_REQUIRE(pairs >= C * *P, "%s: the workspace holds %lld pairs, C P = %lld x %lld are used", who, (long long)pairs, (long long)C, (long long)*P);
+    UCNERF_REQUIRE(((uintptr_t)ws & 7) == 0, "%s: the workspace is not 8-byte aligned", who);
+    return UCNERF_OK;
+}
+
+int ucnerf_bn_bwd_reduce(const ucnerf_bn_bwd_reduce_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "bn_bwd_reduce: null params");
+    int64_t N, P;
+    if (int rc = bn_bwd_common("bn_bwd_reduce", p->n, p->C, p->S, p->workspace_pairs, p->eps, p->g, p->y, p->saved_mean, p->saved_var, p->weight, p->bias, p->workspace, &N, &P))
+        return rc;
+    Walk w;
+    w.C = p->C; w.S = p->S; w.N = (unsigned)N; w.S32 = (unsigned)p->S;
+    w.vec = p->S % 4 == 0 && aligned16(p->g) && aligned16(p->y);
+    BwdArgs a;
+    a.g = p->g; a.y = p->y; a.mean = p->saved_mean; a.var = p->saved_var; a.gamma = p->weight; a.beta = p->bias; a.eps = p->eps; a.relu = p->relu != 0; a.P = (int)P;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)P, (unsigned)p->C), dim3(BN_STATS_THREADS), 0, (hipStream_t)stream, a, w, (unsigned)bn_slice(N, P), p->workspace);
+    return check_launch("bn_bwd_reduce");
+}
+
+int ucnerf_bn_bwd_apply(const ucnerf_bn_bwd_apply_params* p, void* stream) {
+    UCNERF_REQUIRE(p, "bn_bwd_apply: null params");
+    int64_t N, P;
+    if (int rc = bn_bwd_common("bn_bwd_apply", p->n, p->C, p->S, p->workspace_pairs, p->eps, p->g, p->y, p->saved_mean, p->saved_var, p->weight, p->bias, p->workspace, &N, &P))
+        return rc;
+    UCNERF_REQUIRE(p->grad_y && p->grad_weight && p->grad_bias, "bn_bwd_apply: null grad_y, grad_weight or grad_bias");
+    Walk w;
+    w.C = p->C; w.S = p->S; w.N = (unsigned)N; w.S32 = (unsigned)p->S;
+    w.vec = p->S % 4 == 0 && aligned16(p->g) && aligned16(p->y) && aligned16(p->grad_y);
+    BwdArgs a;
+    a.g = p->g; a.y = p->y; a.mean = p->saved_mean; a.var = p->saved_var; a.gamma = p->weight; a.beta = p->bias; a.eps = p->eps; a.relu = p->relu != 0; a.P = (int)P;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((N + BN_APPLY_CHUNK - 1) / BN_APPLY_CHUNK), (unsigned)p->C), dim3(BN_APPLY_THREADS), 0, (hipStream_t)stream, a, w,
+                       p->workspace, p->grad_y, p->grad_weight, p->grad_bias);
+    return check_launch("bn_bwd_apply");
 }
 
 }  // extern "C"

@@ -447,6 +447,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_conv2d_pack_params); SZ(ucnerf_conv2d_params); SZ(ucnerf_maxpool2d_params); SZ(ucnerf_lpips_layer_params); SZ(ucnerf_lpips_alex_params);
     SZ(ucnerf_conv3d_pack_params); SZ(ucnerf_conv3d_params);
     SZ(ucnerf_bn_stats_params); SZ(ucnerf_bn_apply_params);
+    SZ(ucnerf_conv3d_wgrad_params); SZ(ucnerf_bn_bwd_reduce_params); SZ(ucnerf_bn_bwd_apply_params);
 #undef SZ
     return -1;
 }

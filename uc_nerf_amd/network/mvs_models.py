@@ -28,6 +28,7 @@ from .. import ops
 
 INFERENCE_ROUTES = ("device", "torch")
 BATCH_STATS_ROUTES = ("torch", "device")
+TRAINING_ROUTES = ("torch", "device")
 
 
 class Conv2d(nn.Module):
@@ -140,6 +141,13 @@ def _check_batch_stats(batch_stats):
     return batch_stats
 
 
+def _check_training(training):
+    if training not in TRAINING_ROUTES:
+        raise ValueError("uc_nerf_amd: training=%r -- \"torch\" (torch's layers whenever grad is enabled) or \"device\" (the HIP forward and backward "
+                         "kernels under train() + grad, with inference=\"device\")" % (training,))
+    return training
+
+
 def _device_route(module, x):
     return module.inference == "device" and not module.training and not torch.is_grad_enabled() and x.is_cuda
 
@@ -147,6 +155,14 @@ def _device_route(module, x):
 def _batch_stats_route(module, x):
     """train() + no_grad on the device with batch_stats="device", every batch-norm keeping running statistics with a float momentum."""
     if not (module.inference == "device" and module.batch_stats == "device" and module.training and not torch.is_grad_enabled() and x.is_cuda):
+        return False
+    return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
+               for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
+
+
+def _training_route(module, x):
+    """train() + grad enabled on the device with training="device", every batch-norm keeping running statistics with a float momentum."""
+    if not (module.training_route == "device" and module.inference == "device" and module.training and torch.is_grad_enabled() and x.is_cuda):
         return False
     return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
                for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
@@ -257,14 +273,17 @@ class CostRegNet(nn.Module):
     """mvs_models.py:412-443: variance volume [n,C,D,H,W] -> (cost [n,c,D,H,W], logits [n,1,D,H,W]); an hourglass of seven convolutions, three
     transposed ones with skip additions and the one-channel `prob`.  Names as in the reference, so `cost_regularization.N.*` keys load strictly.
     Two routes as in FeatureNet; the device route is eleven `ops.conv3d` launches (batch-norm folded, the skip additions inside the launches)
-    and needs D, H and W divisible by 8 -- as the reference's additions do."""
+    and needs D, H and W divisible by 8 -- as the reference's additions do.  training="device" adds a fourth, under train() + grad enabled: every
+    layer is `ops.conv3d_bn_train` (`ops.conv3d_train` for `prob`), forward and backward on the HIP kernels, the running statistics moved as
+    torch moves them; the default "torch" keeps torch's layers there."""
 
     ORDER = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11", "prob")
 
-    def __init__(self, in_channels, base_channels, inference="device", batch_stats="torch"):
+    def __init__(self, in_channels, base_channels, inference="device", batch_stats="torch", training="torch"):
         super().__init__()
         self.inference = _check_route(inference)
         self.batch_stats = _check_batch_stats(batch_stats)
+        self.training_route = _check_training(training)      # (nn.Module owns the attribute `training`)
         c = base_channels
         self.conv0 = Conv3d(in_channels, c, padding=1)
         self.conv1 = Conv3d(c, 2 * c, stride=2, padding=1)
@@ -279,6 +298,15 @@ class CostRegNet(nn.Module):
         self.prob = nn.Conv3d(c, 1, 3, stride=1, padding=1, bias=False)
         self._cache = _InferenceCache()
         self._raw_cache = _InferenceCache(_conv_weights)
+        self._dgrad_cache = _InferenceCache(_conv_weights)
+
+    def _dgrad(self):
+        out = {}
+        for name in self.ORDER:
+            layer = getattr(self, name)
+            conv = layer.conv if hasattr(layer, "conv") else layer
+            out[name] = ops.conv3d_dgrad_pack(conv.weight.detach().float(), conv.stride[0], 1, getattr(layer, "transposed", False))
+        return out
 
     def _fold(self):
         out = {}
@@ -303,6 +331,8 @@ class CostRegNet(nn.Module):
             return self._forward_device(x)
         if _batch_stats_route(self, x):
             return self._forward_device(x, batch_stats=True)
+        if _training_route(self, x):
+            return self._forward_train(x)
         conv0 = self.conv0(x)
         conv2 = self.conv2(self.conv1(conv0))
         conv4 = self.conv4(self.conv3(conv2))
@@ -333,6 +363,29 @@ class CostRegNet(nn.Module):
         x = conv("conv9", x, 2, skip=conv2)
         cost = conv("conv11", x, 2, skip=conv0)
         return cost, conv("prob", cost, relu=False)
+
+
+    def _forward_train(self, x):
+        if x.dim() != 5 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
+            raise RuntimeError("uc_nerf_amd CostRegNet: the device route takes [n,C,D,H,W] with D, H and W divisible by 8 (three halvings, three "
+                               "doublings and the skip additions between them), got %s" % (tuple(x.shape),))
+        f, d = self._raw_cache.get(self, self._raw), self._dgrad_cache.get(self, self._dgrad)
+
+        def conv(name, t, stride=1, skip=None):
+            layer = getattr(self, name)
+            bn = layer.bn
+            return ops.conv3d_bn_train(t, layer.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                       momentum=bn.momentum, eps=bn.eps, stride=stride, pad=1, relu=layer.relu, skip=skip,
+                                       transposed=layer.transposed, packed=f[name][0], packed_dgrad=d[name])
+
+        conv0 = conv("conv0", x)
+        conv2 = conv("conv2", conv("conv1", conv0, 2))
+        conv4 = conv("conv4", conv("conv3", conv2, 2))
+        x = conv("conv6", conv("conv5", conv4, 2))
+        x = conv("conv7", x, 2, skip=conv4)
+        x = conv("conv9", x, 2, skip=conv2)
+        cost = conv("conv11", x, 2, skip=conv0)
+        return cost, ops.conv3d_train(cost, self.prob.weight, 1, 1, packed=f["prob"][0], packed_dgrad=d["prob"])
 
 
 def mvs_depth_regression(p, depth_values):                 # mvs_models.py:574-579
@@ -447,15 +500,18 @@ class CascadeMVSNet(nn.Module):
 
     @classmethod
     def with_cnns(cls, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
-                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch"):
+                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch", training="torch"):
         """The net with its own `FeatureNet` and one `CostRegNet` per stage (mvs_models.py:678-687), so that a reference checkpoint loads and
         runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch");
-        `batch_stats`: the one they take under train() + no_grad ("torch", or "device" with inference="device")."""
+        `batch_stats`: the one they take under train() + no_grad ("torch", or "device" with inference="device"); `training`: the one the
+        `CostRegNet`s take under train() + grad enabled ("torch", or "device" with inference="device": forward and backward on the HIP kernels.
+        `FeatureNet` keeps training through torch's layers)."""
         if share_cr:
             raise NotImplementedError("uc_nerf_amd CascadeMVSNet.with_cnns: share_cr=True (one regulariser for stages whose feature channels "
                                       "differ; the reference's constructor fails on it too) -- hand a module in through CascadeMVSNet(...)")
         feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference, batch_stats=batch_stats)
-        regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference, batch_stats=batch_stats)
+        regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference, batch_stats=batch_stats,
+                                         training=training)
                               for i in range(len(ndepths))])
         return cls(view_num, ndepths, depth_interals_ratio, share_cr, grad_method, arch_mode, cr_base_chs, feature=feature, cost_regularization=regs)
 

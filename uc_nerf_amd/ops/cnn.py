@@ -1,8 +1,10 @@
-"""The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip) and the batch-statistic batch-norm of both CNNs (csrc/bn.hip)."""
+"""The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip), the batch-statistic batch-norm of both CNNs (csrc/bn.hip), and
+their backward: the weight gradient (csrc/conv3d_bwd.hip), the input gradient on the forward kernel, the batch-norm backward with the ReLU mask,
+and the differentiable layer CostRegNet's training route is made of."""
 import torch
 
 from .. import _lib as L
-from ._core import _f32, _launch, _ptr
+from ._core import _dev, _f32, _launch, _ptr
 
 
 class PackedConv3d:
@@ -123,3 +125,208 @@ def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tra
     if given is not None:
         out = given                                        # the caller's own tensor (y itself for in place), not the detached alias
     return (out, saved[0], saved[1]) if return_stats else out
+
+
+def _conv_out(size, stride, pad):
+    return tuple((s + 2 * pad - 3) // stride + 1 for s in size)
+
+
+def conv3d_wgrad(x, grad_y, stride=1, pad=1, transposed=False):
+    """The weight gradient of `conv3d` with a K = 3 kernel (csrc/conv3d_bwd.hip: exact float32 on the matrix cores, split over chunks of the
+    voxels and folded in ascending chunk order, no atomics, two calls give the same bits).  x [n,cin,D,H,W] the layer's input, grad_y the
+    gradient of its output ([n,cout,OD,OH,OW]; transposed: [n,cout,2D,2H,2W]) -> [cout,cin,3,3,3] (transposed: [cin,cout,3,3,3])."""
+    x, grad_y = _f32(x.detach(), "x"), _f32(grad_y.detach(), "grad_y")
+    transposed, stride, pad = bool(transposed), int(stride), int(pad)
+    if x.dim() != 5 or grad_y.dim() != 5 or x.device != grad_y.device or x.shape[0] != grad_y.shape[0] or 0 in x.shape[1:] or 0 in grad_y.shape[1:]:
+        raise RuntimeError("uc_nerf_amd.conv3d_wgrad: x [n,cin,D,H,W] and grad_y [n,cout,...] on one device, got %s and %s" % (tuple(x.shape), tuple(grad_y.shape)))
+    n, cin, D, H, W = x.shape
+    cout = grad_y.shape[1]
+    floats = L.lib().ucnerf_conv3d_wgrad_workspace_floats(n, cin, cout, D, H, W, 3, stride, pad, int(transposed))
+    if floats < 0:
+        raise RuntimeError("uc_nerf_amd.conv3d_wgrad: %s" % L.lib().ucnerf_last_error().decode())
+    want = tuple(2 * s for s in (D, H, W)) if transposed else _conv_out((D, H, W), stride, pad)
+    if tuple(grad_y.shape[2:]) != want:
+        raise RuntimeError("uc_nerf_amd.conv3d_wgrad: grad_y must be [%d,%d,%d,%d,%d] for x %s with stride=%d pad=%d transposed=%s, got %s"
+                           % ((n, cout) + want + (tuple(x.shape), stride, pad, transposed, tuple(grad_y.shape))))
+    grad_w = torch.empty((cin, cout, 3, 3, 3) if transposed else (cout, cin, 3, 3, 3), device=x.device)
+    workspace = torch.empty(floats, device=x.device)
+    p = L.Conv3dWgradParams()
+    p.n, p.cin, p.D, p.H, p.W, p.cout, p.K, p.stride, p.pad, p.transposed = n, cin, D, H, W, cout, 3, stride, pad, int(transposed)
+    p.workspace_floats, p.x, p.grad_y, p.workspace, p.grad_weight = floats, _ptr(x), _ptr(grad_y), _ptr(workspace), _ptr(grad_w)
+    _launch("ucnerf_conv3d_wgrad", p, x.device)
+    return grad_w
+
+
+def conv3d_dgrad_pack(weight, stride=1, pad=1, transposed=False):
+    """The K = 3 weight of a layer packed for `conv3d_dgrad` (a copy: the layer's weight may change afterwards).  Stride 1 (pad 1): the
+    transposed, flipped weight for the forward form; stride 2 (pad 1): the same tensor read as a transposed convolution's [cin' = cout,
+    cout' = cin,3,3,3]; a transposed layer: its weight read as a forward one's [cout' = cin, cin' = cout,3,3,3]."""
+    transposed, stride, pad = bool(transposed), int(stride), int(pad)
+    if not torch.is_tensor(weight) or weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise RuntimeError("uc_nerf_amd.conv3d_dgrad: the weight must be [cout,cin,3,3,3] ([cin,cout,3,3,3] transposed)")
+    if transposed:
+        if (stride, pad) != (2, 1):
+            raise RuntimeError("uc_nerf_amd.conv3d_dgrad: the transposed form is stride=2 pad=1 (output_padding 1), got stride=%d pad=%d" % (stride, pad))
+        return conv3d_pack(weight, transposed=False)
+    if pad != 1 or stride not in (1, 2):
+        raise RuntimeError("uc_nerf_amd.conv3d_dgrad: stride 1 or 2 with pad 1 is built, got stride=%d pad=%d" % (stride, pad))
+    if stride == 2:
+        return conv3d_pack(weight, transposed=True)
+    return conv3d_pack(_f32(weight.detach(), "weight").transpose(0, 1).flip(2, 3, 4).contiguous(), transposed=False)
+
+
+def conv3d_dgrad(grad_y, weight, x_shape, stride=1, pad=1, transposed=False):
+    """The input gradient of `conv3d` with a K = 3 kernel, on `conv3d` itself (zero bias, no ReLU, no skip): `weight` the layer's raw weight or
+    what `conv3d_dgrad_pack` made of it, `x_shape` the layer input's [n,cin,D,H,W].  A stride-2 layer needs even D, H and W (an odd size would
+    need output_padding 0, which is not built): RuntimeError otherwise."""
+    transposed, stride, pad = bool(transposed), int(stride), int(pad)
+    x_shape = tuple(int(v) for v in x_shape)
+    if len(x_shape) != 5 or not torch.is_tensor(grad_y) or grad_y.dim() != 5 or min(x_shape) < 1:
+        raise RuntimeError("uc_nerf_amd.conv3d_dgrad: grad_y must be [n,cout,...] and x_shape [n,cin,D,H,W], got %s and %s"
+                           % (tuple(grad_y.shape) if torch.is_tensor(grad_y) else type(grad_y), x_shape))
+    if transposed:
+        if (stride, pad) != (2, 1):
+            raise RuntimeError("uc_nerf_amd.conv3d_dgrad: the transposed form is stride=2 pad=1 (output_padding 1), got stride=%d pad=%d" % (stride, pad))
+        want, route = tuple(2 * s for s in x_shape[2:]), dict(stride=2, pad=1, transposed=False)
+    elif stride == 2:
+        if pad != 1 or any(s % 2 for s in x_shape[2:]):
+            raise RuntimeError("uc_nerf_amd.conv3d_dgrad: a stride-2 layer needs pad 1 and even D, H, W (an odd size needs output_padding 0, which is "
+                               "not built), got x_shape %s pad=%d" % (x_shape, pad))
+        want, route = tuple(s // 2 for s in x_shape[2:]), dict(stride=2, pad=1, transposed=True)
+    else:
+        if stride != 1 or pad != 1:
+            raise RuntimeError("uc_nerf_amd.conv3d_dgrad: stride 1 or 2 with pad 1 is built, got stride=%d pad=%d" % (stride, pad))
+        want, route = x_shape[2:], dict(stride=1, pad=1, transposed=False)
+    if tuple(grad_y.shape[2:]) != want or grad_y.shape[0] != x_shape[0]:
+        raise RuntimeError("uc_nerf_amd.conv3d_dgrad: grad_y must be [%d,cout,%d,%d,%d] for x_shape %s, got %s" % ((x_shape[0],) + want + (x_shape, tuple(grad_y.shape))))
+    grad_y = _f32(grad_y.detach(), "grad_y")
+    w = weight if isinstance(weight, PackedConv3d) else conv3d_dgrad_pack(weight, stride, pad, transposed)
+    if w.cout != x_shape[1] or w.cin != grad_y.shape[1] or w.K != 3 or w.transposed != route["transposed"]:
+        raise RuntimeError("uc_nerf_amd.conv3d_dgrad: grad_y %s and x_shape %s do not fit the weight (the layer's cin=%d cout=%d, packed transposed=%s)"
+                           % (tuple(grad_y.shape), x_shape, w.cout, w.cin, w.transposed))
+    zero = torch.zeros(w.cout, device=grad_y.device)
+    return conv3d(grad_y, w, zero, relu=False, skip=None, **route)
+
+
+def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1e-5, relu=True, out=None):
+    """The backward of `batch_norm_train` (csrc/bn.hip: `ucnerf_bn_bwd_reduce` then `ucnerf_bn_bwd_apply`, float64 sums in a fixed order, nothing
+    read back): grad_out the gradient of act(bn(y)), y the tensor the forward normalised, saved_mean / saved_var what it returned with
+    `return_stats`; the ReLU's mask is recomputed from y bit for bit.  `out`: a tensor like y for grad_y, grad_out itself for in place.
+    -> (grad_y, grad_weight, grad_bias).  The skip's gradient is grad_out itself."""
+    for t, name in ((grad_out, "grad_out"), (y, "y")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.is_contiguous() and t.numel() > 0):
+            raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a non-empty contiguous float32 [n,C,*spatial] tensor on a ROCm device" % name)
+    if grad_out.shape != y.shape or grad_out.device != y.device:
+        raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: grad_out %s and y %s differ" % (tuple(grad_out.shape), tuple(y.shape)))
+    grad_out, y = grad_out.detach(), y.detach()
+    n, C = y.shape[0], y.shape[1]
+    S = y.numel() // (n * C)
+    if not float(eps) > 0.0:
+        raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: eps=%r (a positive float)" % (eps,))
+    per_channel = []
+    for t, name in ((saved_mean, "saved_mean"), (saved_var, "saved_var"), (weight, "weight"), (bias, "bias")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == (C,) and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a contiguous float32 [%d] tensor on y's device" % (name, C))
+        per_channel.append(t.detach())
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == y.device and out.shape == y.shape and out.is_contiguous()):
+        raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: out must be a contiguous float32 tensor of y's shape %s on its device" % (tuple(y.shape),))
+    P = L.lib().ucnerf_bn_partials(n, S)
+    if P < 0:
+        raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
+                           % (tuple(y.shape),))
+    grad_y = torch.empty_like(y) if out is None else out.detach()
+    workspace = torch.empty((C, P, 2), dtype=torch.float64, device=y.device)
+    grads = torch.empty((2, C), device=y.device)
+    r = L.BnBwdReduceParams()
+    a = L.BnBwdApplyParams()
+    for q in (r, a):
+        q.n, q.C, q.S, q.workspace_pairs, q.eps, q.relu = n, C, S, C * P, float(eps), int(bool(relu))
+        q.g, q.y, q.workspace = _ptr(grad_out), _ptr(y), _ptr(workspace)
+        q.saved_mean, q.saved_var, q.weight, q.bias = (_ptr(t) for t in per_channel)
+    a.grad_y, a.grad_weight, a.grad_bias = _ptr(grad_y), _ptr(grads[0]), _ptr(grads[1])
+    _launch("ucnerf_bn_bwd_reduce", r, y.device)
+    _launch("ucnerf_bn_bwd_apply", a, y.device)
+    return (grad_y if out is None else out), grads[0], grads[1]
+
+
+class _Conv3dBnTrain(torch.autograd.Function):
+    """One CostRegNet layer in training mode: conv3d with the raw weight, then batch_norm_train out of place (the raw output survives for the
+    backward).  The dgrad weight is packed in the forward, so the backward uses the weight's values as of the forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, skip, buffers, momentum, eps, stride, pad, relu, transposed, packed, packed_dgrad):
+        running_mean, running_var, nbt = buffers
+        w = packed if packed is not None else conv3d_pack(weight, transposed)
+        y = conv3d(x, w, torch.zeros(w.cout, device=x.device), stride=stride, pad=pad, relu=False, skip=None, transposed=transposed)
+        out, mean, var = batch_norm_train(y, gamma, beta, running_mean, running_var, nbt, momentum=momentum, eps=eps, relu=relu, skip=skip, out=None,
+                                          return_stats=True)
+        ctx.layer = (stride, pad, bool(relu), bool(transposed), float(eps), tuple(x.shape))
+        ctx.packed_dgrad = None
+        if ctx.needs_input_grad[0]:
+            ctx.packed_dgrad = packed_dgrad if packed_dgrad is not None else conv3d_dgrad_pack(weight, stride, pad, transposed)
+        ctx.save_for_backward(x.detach(), y, mean, var, gamma, beta)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, y, mean, var, gamma, beta = ctx.saved_tensors
+        stride, pad, relu, transposed, eps, x_shape = ctx.layer
+        grad_out = grad_out.contiguous()
+        grad_skip = grad_out if ctx.needs_input_grad[4] else None
+        grad_y, grad_gamma, grad_beta = batch_norm_train_bwd(grad_out, y, mean, var, gamma, beta, eps=eps, relu=relu)
+        grad_w = conv3d_wgrad(x, grad_y, stride, pad, transposed) if ctx.needs_input_grad[1] else None
+        grad_x = conv3d_dgrad(grad_y, ctx.packed_dgrad, x_shape, stride, pad, transposed) if ctx.needs_input_grad[0] else None
+        return (grad_x, grad_w, grad_gamma if ctx.needs_input_grad[2] else None, grad_beta if ctx.needs_input_grad[3] else None, grad_skip) + (None,) * 9
+
+
+class _Conv3dTrain(torch.autograd.Function):
+    """A bare K = 3 convolution without bias (CostRegNet's `prob`) with its backward on the device."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, pad, packed, packed_dgrad):
+        w = packed if packed is not None else conv3d_pack(weight, False)
+        y = conv3d(x, w, torch.zeros(w.cout, device=x.device), stride=stride, pad=pad, relu=False, skip=None, transposed=False)
+        ctx.layer = (stride, pad, tuple(x.shape))
+        ctx.packed_dgrad = None
+        if ctx.needs_input_grad[0]:
+            ctx.packed_dgrad = packed_dgrad if packed_dgrad is not None else conv3d_dgrad_pack(weight, stride, pad, False)
+        ctx.save_for_backward(x.detach())
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, = ctx.saved_tensors
+        stride, pad, x_shape = ctx.layer
+        grad_y = grad_y.contiguous()
+        grad_w = conv3d_wgrad(x, grad_y, stride, pad, False) if ctx.needs_input_grad[1] else None
+        grad_x = conv3d_dgrad(grad_y, ctx.packed_dgrad, x_shape, stride, pad, False) if ctx.needs_input_grad[0] else None
+        return grad_x, grad_w, None, None, None, None
+
+
+def _train_weight(weight, who):
+    if not (torch.is_tensor(weight) and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3)):
+        raise RuntimeError("uc_nerf_amd.%s: the weight must be a float32 [cout,cin,3,3,3] ([cin,cout,3,3,3] transposed) tensor on a ROCm device" % who)
+
+
+def conv3d_bn_train(x, weight, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, stride=1, pad=1, relu=True,
+                    skip=None, transposed=False, packed=None, packed_dgrad=None):
+    """act(batch_norm(conv3d(x, weight))) (+ skip) with the batch's own statistics, DIFFERENTIABLE (once) in x, weight, bn_weight, bn_bias and
+    skip, forward and backward on the device: `conv3d` and `batch_norm_train` (the running statistics move exactly as there), then
+    `batch_norm_train_bwd`, `conv3d_wgrad` (only if the weight needs a gradient) and `conv3d_dgrad` (only if x does).  K = 3, pad 1, stride 1 or 2
+    (even sizes), or the transposed form.  `packed` / `packed_dgrad`: what `conv3d_pack(weight, transposed)` / `conv3d_dgrad_pack(weight, ...)`
+    made of the weight AS IT IS NOW (a module's cache); without them the weight is packed here.  Either way the backward uses the weight's
+    values as of this call, whatever happens to the tensor afterwards."""
+    _dev(x)
+    _train_weight(weight, "conv3d_bn_train")
+    return _Conv3dBnTrain.apply(x, weight, bn_weight, bn_bias, skip, (running_mean, running_var, num_batches_tracked), momentum, float(eps), int(stride),
+                                int(pad), bool(relu), bool(transposed), packed, packed_dgrad)
+
+
+def conv3d_train(x, weight, stride=1, pad=1, packed=None, packed_dgrad=None):
+    """conv3d(x, weight) with a bias-free K = 3 kernel, differentiable (once) in x and weight on the device (`conv3d`, `conv3d_wgrad`,
+    `conv3d_dgrad`); `packed` / `packed_dgrad` as in `conv3d_bn_train`."""
+    _dev(x)
+    _train_weight(weight, "conv3d_train")
+    return _Conv3dTrain.apply(x, weight, int(stride), int(pad), packed, packed_dgrad)
