@@ -1424,6 +1424,71 @@ struct ucnerf_composite_fold_params {
 typedef struct ucnerf_composite_fold_params ucnerf_composite_fold_params;
 int ucnerf_composite_fold_grads(const ucnerf_composite_fold_params* p, void* stream);
 
+/* Training FeatureNet on the device: the backward of ucnerf_conv2d_bias_relu for the layers of the feature pyramid (added to ABI v6; nothing
+ * above moved; structs declared with a tag: mirrored in _lib.ADDED_STRUCTS).  float32, NCHW contiguous.  No atomics, plain vector stores only,
+ * two calls give the same bits.  The INPUT gradient of a stride-1 layer needs no entry point of its own: it is ucnerf_conv2d_bias_relu on grad_y
+ * with the weight transposed and flipped, zero bias, no ReLU (uc_nerf_amd.ops.conv2d_dgrad).
+ *
+ * ucnerf_conv2d_wgrad: grad_weight[co][ci][ky][kx] = sum over (img, oy, ox) of grad_y[img,co,oy,ox] x[img,ci, stride oy - pad + ky, stride ox - pad + kx],
+ *   a tap outside the image entering as the product a * +0.  K 1, 3 or 5, pad = (K - 1) / 2, stride 1, or 2 with K 3 or 5;
+ *   OH = (H + 2 pad - K) / stride + 1, OW likewise.  Exact fp32 products and fp32 accumulation on v_mfma_f32_16x16x4_f32: rows = cout, columns =
+ *   the flat (ci, ky, kx), and the output pixels v = (img OH + oy) OW + ox are the reduction dimension, cut into chunks of whole output rows.
+ *   SUMMATION ORDER (fixed, part of the interface).  With / the integer division and ceil(a / b) = (a + b - 1) / b:
+ *     OW4 = 4 ceil(OW / 4);  SW = min(OW4, 128);  WP = stride (SW - 1) + K;  CG0 = min(cin, 256 / (K K));
+ *     RR = 1 when OW4 > 128 or no larger value fits, else the largest r in 2 .. 128 / OW4 with CG0 ((r - 1) stride + K) WP <= 11264;
+ *     CG = min(CG0, 11264 / (((RR - 1) stride + K) WP));  tiles = ceil(cout / 32) ceil(cin / CG);  G = n OH (the rows of all images);
+ *     C0 = max(1, min(ceil(G / RR), ceil(512 / tiles)));  the chunk length RC = RR ceil(G / (RR C0)) rows;  chunks = ceil(G / RC); chunk c is the
+ *     rows [c RC, min((c + 1) RC, G)), that is the pixels v in [c RC OW, ...).
+ *     Within a chunk P_c = one fmaf chain from +0 over ascending v (the MFMA adds four consecutive pixels of a row per instruction, the lowest
+ *     first; a row whose length is no multiple of 4 is padded with products +0 * +0, which change no bit).  grad_weight = (((+0 + P_0) + P_1)
+ *     + ...) over ascending c, by a second launch.
+ *   workspace: ucnerf_conv2d_wgrad_workspace_floats(...) = chunks cout cin K K floats, laid out [chunk][cout][cin K K], every element overwritten;
+ *     < 0 on a bad argument; pure host.  Limits: cin, cout <= 2^16; n cin H W, n cout OH OW < 2^31; n OH < 2^31 - 1024; cin cout K K < 2^31.
+ *
+ * ucnerf_conv2d_dgrad_s2: the input gradient of a stride-2 layer with K 3 or 5 and pad (K - 1) / 2; H and W (of x) even, so OH = H / 2, OW = W / 2
+ *   (an odd size is UCNERF_EINVAL).  `weight` is the layer's RAW [cout,cin,K,K] weight: nothing is packed.  By parity class of the input pixel:
+ *   py = (iy + pad) & 1, the taps ky = py + 2 jy, jy = 0 .. nky - 1, nky = (K - py + 1) / 2, reach iy from the source row (iy + pad - ky) / 2; px,
+ *   jx, nkx likewise.  grad_x[img,ci,iy,ix] = sum over k' = (co nky + jy) nkx + jx, ascending, of grad_y[img,co,(iy + pad - ky) / 2,
+ *   (ix + pad - kx) / 2] w[co,ci,ky,kx], a source outside grad_y contributing +0, in the blocked order of ucnerf_conv2d_bias_relu: runs of 32
+ *   consecutive k', each an fmaf chain from +0 (the last one may be shorter), T = (((+0 + S_0) + S_1) + ...) ascending.  Exact fp32, one thread per
+ *   element.  Limits: n <= 16383; cin <= 65535; n cin H W, cin cout K K < 2^31.
+ *
+ * ucnerf_conv2d_bias_grad: grad_bias[co] = sum of grad_y[:,co,:,:] ([n,cout,OH,OW]) in float64, rounded once.  Order: thread t of 1024 adds,
+ *   image after image, the pixels s = t, t + 1024, ... of the channel's plane ascending, from 0; then for d = 512, 256, .. 1 thread t < d adds
+ *   thread t + d's sum.  n cout OH OW < 2^31.
+ *
+ * UCNERF_EINVAL with ucnerf_last_error before any device call, for all three: NULL params or array, negative n, non-positive sizes, a K /
+ *   stride / pad outside the above, an odd H or W (dgrad_s2), workspace_floats that does not match the query (wgrad).  n == 0 is success, nothing
+ *   launched. */
+struct ucnerf_conv2d_wgrad_params {
+    int32_t n, cin, H, W, cout, K, stride, pad;   /* of the layer: x is [n,cin,H,W] */
+    int64_t workspace_floats;  /* floats `workspace` holds = ucnerf_conv2d_wgrad_workspace_floats(the same arguments) */
+    const float* x;            /* [n,cin,H,W] */
+    const float* grad_y;       /* [n,cout,OH,OW] */
+    float* workspace;          /* overwritten */
+    float* grad_weight;        /* [cout,cin,K,K], overwritten */
+};
+typedef struct ucnerf_conv2d_wgrad_params ucnerf_conv2d_wgrad_params;
+int64_t ucnerf_conv2d_wgrad_workspace_floats(int32_t n, int32_t cin, int32_t cout, int32_t H, int32_t W, int32_t K, int32_t stride, int32_t pad);
+int ucnerf_conv2d_wgrad(const ucnerf_conv2d_wgrad_params* p, void* stream);
+
+struct ucnerf_conv2d_dgrad_s2_params {
+    int32_t n, cin, H, W, cout, K;   /* of the layer: grad_x is [n,cin,H,W] */
+    const float* grad_y;       /* [n,cout,H/2,W/2] */
+    const float* weight;       /* [cout,cin,K,K], the layer's raw weight */
+    float* grad_x;             /* [n,cin,H,W], overwritten */
+};
+typedef struct ucnerf_conv2d_dgrad_s2_params ucnerf_conv2d_dgrad_s2_params;
+int ucnerf_conv2d_dgrad_s2(const ucnerf_conv2d_dgrad_s2_params* p, void* stream);
+
+struct ucnerf_conv2d_bias_grad_params {
+    int32_t n, cout, OH, OW;
+    const float* grad_y;       /* [n,cout,OH,OW] */
+    float* grad_bias;          /* [cout], overwritten */
+};
+typedef struct ucnerf_conv2d_bias_grad_params ucnerf_conv2d_bias_grad_params;
+int ucnerf_conv2d_bias_grad(const ucnerf_conv2d_bias_grad_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

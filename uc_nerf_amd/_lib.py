@@ -240,6 +240,19 @@ class BnBwdApplyParams(C.Structure):
                 ("grad_weight", vp), ("grad_bias", vp)]
 
 
+class Conv2dWgradParams(C.Structure):
+    _fields_ = [("n", i32), ("cin", i32), ("H", i32), ("W", i32), ("cout", i32), ("K", i32), ("stride", i32), ("pad", i32),
+                ("workspace_floats", C.c_int64), ("x", vp), ("grad_y", vp), ("workspace", vp), ("grad_weight", vp)]
+
+
+class Conv2dDgradS2Params(C.Structure):
+    _fields_ = [("n", i32), ("cin", i32), ("H", i32), ("W", i32), ("cout", i32), ("K", i32), ("grad_y", vp), ("weight", vp), ("grad_x", vp)]
+
+
+class Conv2dBiasGradParams(C.Structure):
+    _fields_ = [("n", i32), ("cout", i32), ("OH", i32), ("OW", i32), ("grad_y", vp), ("grad_bias", vp)]
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -312,7 +325,9 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv3d_pack_params": Conv3dPackParams, "ucnerf_conv3d_params": Conv3dParams,
                  "ucnerf_bn_stats_params": BnStatsParams, "ucnerf_bn_apply_params": BnApplyParams,
                  "ucnerf_conv3d_wgrad_params": Conv3dWgradParams, "ucnerf_bn_bwd_reduce_params": BnBwdReduceParams,
-                 "ucnerf_bn_bwd_apply_params": BnBwdApplyParams}
+                 "ucnerf_bn_bwd_apply_params": BnBwdApplyParams,
+                 "ucnerf_conv2d_wgrad_params": Conv2dWgradParams, "ucnerf_conv2d_dgrad_s2_params": Conv2dDgradS2Params,
+                 "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -408,6 +423,11 @@ SYMBOLS = {
     "ucnerf_conv3d_wgrad": (C.c_int, [_P, _P]),
     "ucnerf_bn_bwd_reduce": (C.c_int, [_P, _P]),
     "ucnerf_bn_bwd_apply": (C.c_int, [_P, _P]),
+    # FeatureNet's training route: the 2-D weight gradient, the stride-2 input gradient and the bias gradient (additive to ABI v6)
+    "ucnerf_conv2d_wgrad_workspace_floats": (C.c_int64, [C.c_int32] * 8),
+    "ucnerf_conv2d_wgrad": (C.c_int, [_P, _P]),
+    "ucnerf_conv2d_dgrad_s2": (C.c_int, [_P, _P]),
+    "ucnerf_conv2d_bias_grad": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

@@ -5,7 +5,7 @@ result keys; the cost-volume assembly (`homo_warp` + mask count + variance), the
 two stages (previous depth -> next stage's hypothesis volume) run as the HIP kernels `ucnerf_cost_volume` /
 `ucnerf_depth_regress` / `ucnerf_depth_hypotheses`.  The CNNs -- the feature pyramid `FeatureNet` (:309-410) and the 3-D
 regularisation network `CostRegNet` (:412-443) -- are mirrored here with the reference's parameter names: they train through torch's
-layers and, under eval() + no_grad, run on `ucnerf_conv2d_bias_relu` / `ucnerf_conv3d` with the batch-norms folded into the weights.  Under
+layers (or, with training="device", through the HIP forward and backward kernels of csrc/conv2d_bwd.hip, csrc/conv3d_bwd.hip and csrc/bn.hip) and, under eval() + no_grad, run on `ucnerf_conv2d_bias_relu` / `ucnerf_conv3d` with the batch-norms folded into the weights.  Under
 train() + no_grad -- how the reference's validation_step runs them (train.py:226-243) -- batch_stats="device" keeps the convolutions on those
 kernels and normalises with the statistics of the batch itself on `ucnerf_bn_stats` / `ucnerf_bn_apply`, moving the running statistics as torch does.
 `CascadeMVSNet(...)` still takes the caller's modules; `CascadeMVSNet.with_cnns(...)` builds its own.
@@ -162,7 +162,8 @@ def _batch_stats_route(module, x):
 
 def _training_route(module, x):
     """train() + grad enabled on the device with training="device", every batch-norm keeping running statistics with a float momentum."""
-    if not (module.training_route == "device" and module.inference == "device" and module.training and torch.is_grad_enabled() and x.is_cuda):
+    if not (getattr(module, "training_route", "torch") == "device" and module.inference == "device" and module.training and torch.is_grad_enabled()
+            and x.is_cuda):
         return False
     return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
                for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
@@ -186,9 +187,13 @@ class FeatureNet(nn.Module):
     Two routes: torch's layers whenever grad is enabled, the module is in training mode or the input is not on a ROCm device; with
     inference="device", under eval() + no_grad, `ops.conv2d_bias_relu` with the batch-norms folded into weights and biases (packed once, cached).
     batch_stats="device" adds a third, under train() + no_grad: the same convolution launches with the raw weights, each batch-normed layer
-    followed by `ops.batch_norm_train` in place (batch statistics, the running statistics moved as torch moves them)."""
+    followed by `ops.batch_norm_train` in place (batch statistics, the running statistics moved as torch moves them).  training="device" adds a
+    fourth, under train() + grad enabled: the eight batch-normed layers are `ops.conv2d_bn_train`, the five bare ones `ops.conv2d_train`, forward
+    and backward on the HIP kernels (csrc/conv2d_bwd.hip), the running statistics moved as torch moves them; the two nearest-neighbour
+    upsamplings and additions stay torch operations.  The default "torch" keeps torch's layers there.  The attribute `training_route` exists only
+    on a module built with training="device": one without it trains through torch, as every FeatureNet did before the keyword."""
 
-    def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device", batch_stats="torch"):
+    def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device", batch_stats="torch", training="torch"):
         super().__init__()
         if arch_mode != "fpn" or num_stage != 3:
             raise NotImplementedError("uc_nerf_amd FeatureNet: arch_mode=%r num_stage=%r -- only arch_mode=\"fpn\" with num_stage=3 is built"
@@ -196,6 +201,8 @@ class FeatureNet(nn.Module):
         self.arch_mode, self.stride, self.base_channels, self.num_stage = arch_mode, stride, base_channels, num_stage
         self.inference = _check_route(inference)
         self.batch_stats = _check_batch_stats(batch_stats)
+        if _check_training(training) == "device":
+            self.training_route = "device"                   # (nn.Module owns the attribute `training`)
         c = base_channels
         self.conv0 = nn.Sequential(Conv2d(3, c, 3, 1, padding=1), Conv2d(c, c, 3, 1, padding=1))
         self.conv1 = nn.Sequential(Conv2d(c, 2 * c, 5, stride=2, padding=2), Conv2d(2 * c, 2 * c, 3, 1, padding=1), Conv2d(2 * c, 2 * c, 3, 1, padding=1))
@@ -208,6 +215,7 @@ class FeatureNet(nn.Module):
         self.out_channels = [4 * c, 2 * c, c]
         self._cache = _InferenceCache()
         self._raw_cache = _InferenceCache(_conv_weights)
+        self._dgrad_cache = _InferenceCache(_conv_weights)
 
     def _layers(self):
         return list(self.conv0) + list(self.conv1) + list(self.conv2) + [self.out1, self.inner1, self.inner2, self.out2, self.out3]
@@ -226,11 +234,20 @@ class FeatureNet(nn.Module):
             out.append((ops.conv2d_pack(conv.weight.detach().float()), torch.zeros(conv.out_channels, device=conv.weight.device)))
         return out
 
+    def _dgrad(self):
+        out = []
+        for layer in self._layers():
+            conv = layer.conv if hasattr(layer, "conv") else layer
+            out.append(ops.conv2d_dgrad_pack(conv.weight.detach().float(), conv.stride[0], conv.padding[0]))
+        return out
+
     def forward(self, x):
         if _device_route(self, x):
             return self._forward_device(x)
         if _batch_stats_route(self, x):
             return self._forward_device(x, batch_stats=True)
+        if _training_route(self, x):
+            return self._forward_train(x)
         conv0 = self.conv0(x)
         conv1 = self.conv1(conv0)
         conv2 = self.conv2(conv1)
@@ -266,6 +283,32 @@ class FeatureNet(nn.Module):
         outputs["stage2"] = run(11, intra, False)
         intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0, False)
         outputs["stage3"] = run(12, intra, False)
+        return outputs
+
+    def _forward_train(self, x):
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
+            raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
+                               "it), got %s" % (tuple(x.shape),))
+        f, d = self._raw_cache.get(self, self._raw), self._dgrad_cache.get(self, self._dgrad)
+        layers = self._layers()
+
+        def run(i, t):
+            layer = layers[i]
+            if hasattr(layer, "conv"):
+                conv, bn = layer.conv, layer.bn
+                return ops.conv2d_bn_train(t, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                           momentum=bn.momentum, eps=bn.eps, stride=conv.stride[0], pad=conv.padding[0], relu=layer.relu,
+                                           packed=f[i][0], packed_dgrad=d[i])
+            return ops.conv2d_train(t, layer.weight, layer.bias, stride=layer.stride[0], pad=layer.padding[0], packed=f[i][0], packed_dgrad=d[i])
+
+        conv0 = run(1, run(0, x))
+        conv1 = run(4, run(3, run(2, conv0)))
+        conv2 = run(7, run(6, run(5, conv1)))
+        outputs = {"stage1": run(8, conv2)}
+        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + run(9, conv1)
+        outputs["stage2"] = run(11, intra)
+        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0)
+        outputs["stage3"] = run(12, intra)
         return outputs
 
 
@@ -500,16 +543,17 @@ class CascadeMVSNet(nn.Module):
 
     @classmethod
     def with_cnns(cls, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
-                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch", training="torch"):
+                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch", training="torch", feature_training="torch"):
         """The net with its own `FeatureNet` and one `CostRegNet` per stage (mvs_models.py:678-687), so that a reference checkpoint loads and
         runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch");
         `batch_stats`: the one they take under train() + no_grad ("torch", or "device" with inference="device"); `training`: the one the
-        `CostRegNet`s take under train() + grad enabled ("torch", or "device" with inference="device": forward and backward on the HIP kernels.
-        `FeatureNet` keeps training through torch's layers)."""
+        `CostRegNet`s take under train() + grad enabled ("torch", or "device" with inference="device": forward and backward on the HIP kernels);
+        `feature_training`: the same choice for the `FeatureNet`.  With both "device" a training step stays on the project's kernels end to end."""
         if share_cr:
             raise NotImplementedError("uc_nerf_amd CascadeMVSNet.with_cnns: share_cr=True (one regulariser for stages whose feature channels "
                                       "differ; the reference's constructor fails on it too) -- hand a module in through CascadeMVSNet(...)")
-        feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference, batch_stats=batch_stats)
+        feature = FeatureNet(base_channels=8, stride=4, num_stage=len(ndepths), arch_mode=arch_mode, inference=inference, batch_stats=batch_stats,
+                             training=feature_training)
         regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference, batch_stats=batch_stats,
                                          training=training)
                               for i in range(len(ndepths))])

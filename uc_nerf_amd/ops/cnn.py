@@ -1,10 +1,12 @@
 """The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip), the batch-statistic batch-norm of both CNNs (csrc/bn.hip), and
 their backward: the weight gradient (csrc/conv3d_bwd.hip), the input gradient on the forward kernel, the batch-norm backward with the ReLU mask,
-and the differentiable layer CostRegNet's training route is made of."""
+and the differentiable layer CostRegNet's training route is made of.  The same for FeatureNet's 2-D layers: the weight, stride-2 input and bias
+gradients of csrc/conv2d_bwd.hip and the two differentiable layer functions of its training route."""
 import torch
 
 from .. import _lib as L
 from ._core import _dev, _f32, _launch, _ptr
+from .metrics import conv2d_bias_relu, conv2d_pack
 
 
 class PackedConv3d:
@@ -330,3 +332,192 @@ def conv3d_train(x, weight, stride=1, pad=1, packed=None, packed_dgrad=None):
     _dev(x)
     _train_weight(weight, "conv3d_train")
     return _Conv3dTrain.apply(x, weight, int(stride), int(pad), packed, packed_dgrad)
+
+
+def _same_pad(K, pad):
+    return (int(K) - 1) // 2 if pad is None else int(pad)
+
+
+def conv2d_wgrad(x, grad_y, K, stride=1, pad=None):
+    """The weight gradient of `conv2d_bias_relu` (csrc/conv2d_bwd.hip: exact float32 on the matrix cores, split over chunks of whole output rows
+    and folded in ascending chunk order, no atomics, two calls give the same bits).  x [n,cin,H,W] the layer's input, grad_y [n,cout,OH,OW] the
+    gradient of its output; K 1, 3 or 5 with pad (K - 1) / 2 (the default), stride 1, or 2 with K 3 or 5 -> [cout,cin,K,K]."""
+    x, grad_y = _f32(x.detach(), "x"), _f32(grad_y.detach(), "grad_y")
+    K, stride, pad = int(K), int(stride), _same_pad(K, pad)
+    if x.dim() != 4 or grad_y.dim() != 4 or x.device != grad_y.device or x.shape[0] != grad_y.shape[0] or 0 in x.shape[1:] or 0 in grad_y.shape[1:]:
+        raise RuntimeError("uc_nerf_amd.conv2d_wgrad: x [n,cin,H,W] and grad_y [n,cout,OH,OW] on one device, got %s and %s" % (tuple(x.shape), tuple(grad_y.shape)))
+    n, cin, H, W = x.shape
+    cout = grad_y.shape[1]
+    floats = L.lib().ucnerf_conv2d_wgrad_workspace_floats(n, cin, cout, H, W, K, stride, pad)
+    if floats < 0:
+        raise RuntimeError("uc_nerf_amd.conv2d_wgrad: %s" % L.lib().ucnerf_last_error().decode())
+    want = tuple((s + 2 * pad - K) // stride + 1 for s in (H, W))
+    if tuple(grad_y.shape[2:]) != want:
+        raise RuntimeError("uc_nerf_amd.conv2d_wgrad: grad_y must be [%d,%d,%d,%d] for x %s with K=%d stride=%d pad=%d, got %s"
+                           % ((n, cout) + want + (tuple(x.shape), K, stride, pad, tuple(grad_y.shape))))
+    grad_w = torch.empty((cout, cin, K, K), device=x.device)
+    workspace = torch.empty(floats, device=x.device)
+    p = L.Conv2dWgradParams()
+    p.n, p.cin, p.H, p.W, p.cout, p.K, p.stride, p.pad, p.workspace_floats = n, cin, H, W, cout, K, stride, pad, floats
+    p.x, p.grad_y, p.workspace, p.grad_weight = _ptr(x), _ptr(grad_y), _ptr(workspace), _ptr(grad_w)
+    _launch("ucnerf_conv2d_wgrad", p, x.device)
+    return grad_w
+
+
+class PackedDgrad2d:
+    """A layer's weight [cout,cin,K,K] as `conv2d_dgrad` reads it (made by `conv2d_dgrad_pack`): stride 1, the transposed, flipped weight packed
+    for `conv2d_bias_relu`; stride 2, a copy of the raw weight, which `ucnerf_conv2d_dgrad_s2` takes as it is."""
+    __slots__ = ("weight", "cin", "cout", "K", "stride")
+
+    def __init__(self, weight, cin, cout, K, stride):
+        self.weight, self.cin, self.cout, self.K, self.stride = weight, cin, cout, K, stride
+
+
+def conv2d_dgrad_pack(weight, stride=1, pad=None):
+    """The weight of a layer prepared for `conv2d_dgrad` (a copy: the layer's weight may change afterwards).  K odd with pad (K - 1) / 2; stride
+    1, or 2 with K 3 or 5."""
+    if not torch.is_tensor(weight) or weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[2] % 2 == 0 or 0 in weight.shape:
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: the weight must be [cout,cin,K,K] with K odd")
+    cout, cin, K, _ = weight.shape
+    stride, pad = int(stride), _same_pad(K, pad)
+    if pad != (K - 1) // 2 or stride not in (1, 2) or (stride == 2 and K not in (3, 5)):
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: stride 1, or 2 with K 3 or 5, and pad (K - 1) / 2 are built, got K=%d stride=%d pad=%d" % (K, stride, pad))
+    w = _f32(weight.detach(), "weight")
+    if stride == 2:
+        return PackedDgrad2d(w.clone(), cin, cout, K, 2)
+    return PackedDgrad2d(conv2d_pack(w.transpose(0, 1).flip(2, 3).contiguous()), cin, cout, K, 1)
+
+
+def conv2d_dgrad(grad_y, weight, x_shape, stride=1, pad=None):
+    """The input gradient of `conv2d_bias_relu` for a layer with pad (K - 1) / 2: stride 1 on `conv2d_bias_relu` itself (the weight transposed
+    and flipped, zero bias, no ReLU), stride 2 (K 3 or 5) on `ucnerf_conv2d_dgrad_s2`, which works by parity class of the input pixel.  `weight`
+    the layer's raw [cout,cin,K,K] weight or what `conv2d_dgrad_pack` made of it, `x_shape` the layer input's [n,cin,H,W].  A stride-2 layer needs
+    even H and W (an odd size would need output_padding 0, which is not built): RuntimeError otherwise."""
+    stride = int(stride)
+    x_shape = tuple(int(v) for v in x_shape)
+    if len(x_shape) != 4 or not torch.is_tensor(grad_y) or grad_y.dim() != 4 or min(x_shape) < 1:
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: grad_y must be [n,cout,OH,OW] and x_shape [n,cin,H,W], got %s and %s"
+                           % (tuple(grad_y.shape) if torch.is_tensor(grad_y) else type(grad_y), x_shape))
+    if stride == 2 and (x_shape[2] % 2 or x_shape[3] % 2):
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: a stride-2 layer needs even H, W (an odd size needs output_padding 0, which is not built), "
+                           "got x_shape %s" % (x_shape,))
+    w = weight if isinstance(weight, PackedDgrad2d) else conv2d_dgrad_pack(weight, stride, pad)
+    if pad is not None and int(pad) != (w.K - 1) // 2 or stride != w.stride:
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: stride=%d pad=%r do not fit the weight (K=%d, prepared for stride %d, pad %d)"
+                           % (stride, pad, w.K, w.stride, (w.K - 1) // 2))
+    n, cin, H, W = x_shape
+    want = (n, w.cout, H // stride, W // stride)
+    if tuple(grad_y.shape) != want or cin != w.cin:
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: grad_y must be %s for x_shape %s and a weight with cin=%d, got %s" % (want, x_shape, w.cin, tuple(grad_y.shape)))
+    grad_y = _f32(grad_y.detach(), "grad_y")
+    if stride == 1:
+        return conv2d_bias_relu(grad_y, w.weight, torch.zeros(cin, device=grad_y.device), stride=1, pad=(w.K - 1) // 2, relu=False)
+    if w.weight.device != grad_y.device:
+        raise RuntimeError("uc_nerf_amd.conv2d_dgrad: grad_y and the weight are on different devices")
+    grad_x = torch.empty(x_shape, device=grad_y.device)
+    p = L.Conv2dDgradS2Params()
+    p.n, p.cin, p.H, p.W, p.cout, p.K = n, cin, H, W, w.cout, w.K
+    p.grad_y, p.weight, p.grad_x = _ptr(grad_y), _ptr(w.weight), _ptr(grad_x)
+    _launch("ucnerf_conv2d_dgrad_s2", p, grad_y.device)
+    return grad_x
+
+
+def conv2d_bias_grad(grad_y):
+    """The bias gradient of a convolution: grad_y [n,cout,OH,OW] -> [cout], summed in float64 in a fixed order and rounded once."""
+    grad_y = _f32(grad_y.detach(), "grad_y")
+    if grad_y.dim() != 4 or 0 in grad_y.shape[1:]:
+        raise RuntimeError("uc_nerf_amd.conv2d_bias_grad: grad_y must be [n,cout,OH,OW], got %s" % (tuple(grad_y.shape),))
+    n, cout, OH, OW = grad_y.shape
+    out = torch.zeros(cout, device=grad_y.device) if n == 0 else torch.empty(cout, device=grad_y.device)
+    p = L.Conv2dBiasGradParams()
+    p.n, p.cout, p.OH, p.OW, p.grad_y, p.grad_bias = n, cout, OH, OW, _ptr(grad_y), _ptr(out)
+    _launch("ucnerf_conv2d_bias_grad", p, grad_y.device)
+    return out
+
+
+class _Conv2dBnTrain(torch.autograd.Function):
+    """One batch-normed FeatureNet layer in training mode: conv2d_bias_relu with the raw weight, zero bias and no ReLU, then batch_norm_train out
+    of place (the raw output survives for the backward).  The dgrad weight is prepared in the forward, so the backward uses the weight's values
+    as of the forward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, buffers, momentum, eps, stride, pad, relu, packed, packed_dgrad):
+        running_mean, running_var, nbt = buffers
+        w = packed if packed is not None else conv2d_pack(weight)
+        y = conv2d_bias_relu(x, w, torch.zeros(w.cout, device=x.device), stride=stride, pad=pad, relu=False)
+        out, mean, var = batch_norm_train(y, gamma, beta, running_mean, running_var, nbt, momentum=momentum, eps=eps, relu=relu, skip=None, out=None,
+                                          return_stats=True)
+        ctx.layer = (w.K, stride, pad, bool(relu), float(eps), tuple(x.shape))
+        ctx.packed_dgrad = None
+        if ctx.needs_input_grad[0]:
+            ctx.packed_dgrad = packed_dgrad if packed_dgrad is not None else conv2d_dgrad_pack(weight, stride, pad)
+        ctx.save_for_backward(x.detach(), y, mean, var, gamma, beta)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, y, mean, var, gamma, beta = ctx.saved_tensors
+        K, stride, pad, relu, eps, x_shape = ctx.layer
+        grad_y, grad_gamma, grad_beta = batch_norm_train_bwd(grad_out.contiguous(), y, mean, var, gamma, beta, eps=eps, relu=relu)
+        grad_w = conv2d_wgrad(x, grad_y, K, stride, pad) if ctx.needs_input_grad[1] else None
+        grad_x = conv2d_dgrad(grad_y, ctx.packed_dgrad, x_shape, stride, pad) if ctx.needs_input_grad[0] else None
+        return (grad_x, grad_w, grad_gamma if ctx.needs_input_grad[2] else None, grad_beta if ctx.needs_input_grad[3] else None) + (None,) * 8
+
+
+class _Conv2dTrain(torch.autograd.Function):
+    """A bare convolution, with or without bias (FeatureNet's out1, inner1, inner2, out2, out3), with its backward on the device."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, packed, packed_dgrad):
+        w = packed if packed is not None else conv2d_pack(weight)
+        y = conv2d_bias_relu(x, w, bias if bias is not None else torch.zeros(w.cout, device=x.device), stride=stride, pad=pad, relu=False)
+        ctx.layer = (w.K, stride, pad, tuple(x.shape))
+        ctx.packed_dgrad = None
+        if ctx.needs_input_grad[0]:
+            ctx.packed_dgrad = packed_dgrad if packed_dgrad is not None else conv2d_dgrad_pack(weight, stride, pad)
+        ctx.save_for_backward(x.detach())
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, = ctx.saved_tensors
+        K, stride, pad, x_shape = ctx.layer
+        grad_y = grad_y.contiguous()
+        grad_w = conv2d_wgrad(x, grad_y, K, stride, pad) if ctx.needs_input_grad[1] else None
+        grad_b = conv2d_bias_grad(grad_y) if ctx.needs_input_grad[2] else None
+        grad_x = conv2d_dgrad(grad_y, ctx.packed_dgrad, x_shape, stride, pad) if ctx.needs_input_grad[0] else None
+        return grad_x, grad_w, grad_b, None, None, None, None
+
+
+def _train_weight2d(weight, stride, pad, who):
+    if not (torch.is_tensor(weight) and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4 and weight.shape[2] == weight.shape[3]
+            and weight.shape[2] in (1, 3, 5)):
+        raise RuntimeError("uc_nerf_amd.%s: the weight must be a float32 [cout,cin,K,K] tensor with K 1, 3 or 5 on a ROCm device" % who)
+    K = weight.shape[2]
+    if pad != (K - 1) // 2 or stride not in (1, 2) or (stride == 2 and K == 1):
+        raise RuntimeError("uc_nerf_amd.%s: stride 1, or 2 with K 3 or 5, and pad (K - 1) / 2 are built, got K=%d stride=%d pad=%d" % (who, K, stride, pad))
+
+
+def conv2d_bn_train(x, weight, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, stride=1, pad=1, relu=True,
+                    packed=None, packed_dgrad=None):
+    """act(batch_norm(conv2d(x, weight))) with the batch's own statistics, DIFFERENTIABLE (once) in x, weight, bn_weight and bn_bias, forward and
+    backward on the device: `conv2d_bias_relu` and `batch_norm_train` (the running statistics move exactly as there), then
+    `batch_norm_train_bwd`, `conv2d_wgrad` (only if the weight needs a gradient) and `conv2d_dgrad` (only if x does).  K 1, 3 or 5 with pad
+    (K - 1) / 2, stride 1, or 2 with K 3 or 5 (even sizes).  `packed` / `packed_dgrad`: what `conv2d_pack(weight)` / `conv2d_dgrad_pack(weight,
+    stride, pad)` made of the weight AS IT IS NOW (a module's cache); without them the weight is prepared here.  Either way the backward uses the
+    weight's values as of this call, whatever happens to the tensor afterwards."""
+    _dev(x)
+    _train_weight2d(weight, int(stride), int(pad), "conv2d_bn_train")
+    return _Conv2dBnTrain.apply(x, weight, bn_weight, bn_bias, (running_mean, running_var, num_batches_tracked), momentum, float(eps), int(stride), int(pad),
+                                bool(relu), packed, packed_dgrad)
+
+
+def conv2d_train(x, weight, bias=None, stride=1, pad=0, packed=None, packed_dgrad=None):
+    """conv2d(x, weight) + bias, differentiable (once) in x, weight and bias on the device (`conv2d_bias_relu`, `conv2d_wgrad`, `conv2d_dgrad`,
+    `conv2d_bias_grad`; the bias gradient is computed only when the bias requires one); shapes and `packed` / `packed_dgrad` as in
+    `conv2d_bn_train`."""
+    _dev(x)
+    _train_weight2d(weight, int(stride), int(pad), "conv2d_train")
+    return _Conv2dTrain.apply(x, weight, bias, int(stride), int(pad), packed, packed_dgrad)
