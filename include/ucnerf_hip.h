@@ -1489,6 +1489,96 @@ struct ucnerf_conv2d_bias_grad_params {
 typedef struct ucnerf_conv2d_bias_grad_params ucnerf_conv2d_bias_grad_params;
 int ucnerf_conv2d_bias_grad(const ucnerf_conv2d_bias_grad_params* p, void* stream);
 
+/* Grouped batch-statistic batch-norm: the four batch-norm entry points above with the statistics kept PER GROUP OF IMAGES, so that FeatureNet
+ * runs once over all the views of a sample and still normalises every view with its own statistics, as the reference's per-view calls do
+ * (mvs_models.py:701-704).  (Added to ABI v6; nothing above moved; structs declared with a tag: mirrored in _lib.ADDED_STRUCTS.)
+ * y, g, out, skip and grad_y are contiguous float32 [G, n, C, S]; group q is the n images q n .. q n + n - 1, its slab starts at q n C S floats;
+ * within a group a channel has N = n S values, numbered as above.  Every struct is its ungrouped counterpart's with G in front.
+ *
+ * CONTRACT: for every group the values computed are those the ungrouped pair computes on that group's [n,C,S] slab alone, BIT FOR BIT: the same
+ *   P = ucnerf_bn_partials(n, S) and the same slices, the same thread / lane / wave / slice merge order in float64, the same single roundings, the
+ *   same float32 fma(y - mu, s, bias) with IEEE division and square root (both files run the same device functions, csrc/bn_device.h).
+ *   G == 1 gives the ungrouped entry points' bits in every output.
+ * Workspaces: [G,C,P,3] float64 for the statistics (triple j of channel c of group q at ((q C + c) P + j) 3), [G,C,P,2] for the backward.
+ * saved_mean and saved_var are [G,C]: group q's mu and sigma^2.
+ * Running statistics: one block per channel folds the triples of all G groups (thread q group q, the fold of the apply blocks) and one thread
+ *   then applies, in float32 with separate multiplications and additions, for q = 0 .. G - 1 ascending: running_mean = (1 - m) running_mean +
+ *   m mu_q, running_var = (1 - m) running_var + m u_q (u_q the unbiased variance rounded once) -- exactly what G successive ungrouped calls on
+ *   the slabs leave behind.  One thread of the launch adds G to *num_batches_tracked.
+ * Backward: grad_y of group q is the ungrouped backward's on that slab, with saved_mean[q], saved_var[q].  The parameter gradients are sums over
+ *   the groups: the block that owns channel c folds every group's pairs as above, (A_q, B_q), r_q = 1 / sqrt(sigma_q^2 + eps), and adds in
+ *   float64, q ascending, grad_bias[c] = ((A_0 + A_1) + ...), grad_weight[c] = ((B_0 r_0 + B_1 r_1) + ...), each rounded ONCE to float32.  (These are
+ *   not the bits G ungrouped calls followed by float32 additions give: those carry G roundings.)
+ * out may be y, grad_y may be g (not a shifted overlap).  No atomics, every store a plain vector store, nothing is read back, two calls give the
+ *   same bits, the launches can sit in a captured graph.  16-byte accesses where S % 4 == 0 and the arrays are 16-byte aligned (every group base
+ *   then is: a slab is a multiple of four floats), 4-byte ones otherwise, the same values in the same order.
+ * UCNERF_EINVAL before any device call: everything the ungrouped entry refuses for (n, C, S) and its arrays, and G < 1, G > 64, G n S above the
+ *   limit on N (2^31 - 2^20), a G n C S that overflows, workspace_triples / workspace_pairs < G C P. */
+struct ucnerf_bn_stats_groups_params {
+    int64_t G, n, C, S;
+    int64_t workspace_triples; /* at least G C P */
+    const float* y;            /* [G,n,C,S] */
+    double* workspace;         /* [G,C,P,3], overwritten */
+};
+typedef struct ucnerf_bn_stats_groups_params ucnerf_bn_stats_groups_params;
+int ucnerf_bn_stats_groups(const ucnerf_bn_stats_groups_params* p, void* stream);
+
+struct ucnerf_bn_apply_groups_params {
+    int64_t G, n, C, S;
+    int64_t workspace_triples;
+    float eps, momentum;
+    int32_t relu;
+    int32_t reserved;
+    const float* y;            /* [G,n,C,S], as ucnerf_bn_stats_groups read it */
+    const double* workspace;   /* as ucnerf_bn_stats_groups wrote it for the same G, n, C, S */
+    const float* weight;       /* gamma [C] */
+    const float* bias;         /* beta [C] */
+    const float* skip;         /* y's shape, or NULL */
+    float* out;                /* y's shape; may be y */
+    float* saved_mean;         /* [G,C], overwritten */
+    float* saved_var;          /* [G,C], overwritten: the biased variances */
+    float* running_mean;       /* [C], moved G times */
+    float* running_var;        /* [C], moved G times */
+    int64_t* num_batches_tracked;   /* one int64 on the device, G is added */
+};
+typedef struct ucnerf_bn_apply_groups_params ucnerf_bn_apply_groups_params;
+int ucnerf_bn_apply_groups(const ucnerf_bn_apply_groups_params* p, void* stream);
+
+struct ucnerf_bn_bwd_reduce_groups_params {
+    int64_t G, n, C, S;
+    int64_t workspace_pairs;   /* at least G C P */
+    float eps;
+    int32_t relu;
+    const float* g;            /* [G,n,C,S] */
+    const float* y;            /* [G,n,C,S], the forward's input */
+    const float* saved_mean;   /* [G,C] */
+    const float* saved_var;    /* [G,C] */
+    const float* weight;       /* gamma [C] */
+    const float* bias;         /* beta [C] */
+    double* workspace;         /* [G,C,P,2], overwritten */
+};
+typedef struct ucnerf_bn_bwd_reduce_groups_params ucnerf_bn_bwd_reduce_groups_params;
+int ucnerf_bn_bwd_reduce_groups(const ucnerf_bn_bwd_reduce_groups_params* p, void* stream);
+
+struct ucnerf_bn_bwd_apply_groups_params {
+    int64_t G, n, C, S;
+    int64_t workspace_pairs;
+    float eps;
+    int32_t relu;
+    const float* g;
+    const float* y;
+    const float* saved_mean;
+    const float* saved_var;
+    const float* weight;
+    const float* bias;
+    const double* workspace;   /* as ucnerf_bn_bwd_reduce_groups wrote it for the same arguments */
+    float* grad_y;             /* [G,n,C,S]; may be g */
+    float* grad_weight;        /* [C], overwritten: the sum over the groups */
+    float* grad_bias;          /* [C], overwritten: the sum over the groups */
+};
+typedef struct ucnerf_bn_bwd_apply_groups_params ucnerf_bn_bwd_apply_groups_params;
+int ucnerf_bn_bwd_apply_groups(const ucnerf_bn_bwd_apply_groups_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

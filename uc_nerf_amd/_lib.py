@@ -253,6 +253,23 @@ class Conv2dBiasGradParams(C.Structure):
     _fields_ = [("n", i32), ("cout", i32), ("OH", i32), ("OW", i32), ("grad_y", vp), ("grad_bias", vp)]
 
 
+# the grouped batch-norm: each struct is its ungrouped counterpart's with G in front
+class BnStatsGroupsParams(C.Structure):
+    _fields_ = [("G", C.c_int64)] + BnStatsParams._fields_
+
+
+class BnApplyGroupsParams(C.Structure):
+    _fields_ = [("G", C.c_int64)] + BnApplyParams._fields_
+
+
+class BnBwdReduceGroupsParams(C.Structure):
+    _fields_ = [("G", C.c_int64)] + BnBwdReduceParams._fields_
+
+
+class BnBwdApplyGroupsParams(C.Structure):
+    _fields_ = [("G", C.c_int64)] + BnBwdApplyParams._fields_
+
+
 class CasLossParams(C.Structure):
     _fields_ = [("n_stages", i32), ("with_weight", i32), ("n", i32 * 3), ("stage_w", f32 * 3), ("est", vp * 3), ("gt", vp * 3), ("w", vp * 3),
                 ("workspace", vp), ("total", vp), ("stage_loss", vp), ("count", vp), ("wpair", vp * 3), ("status", vp)]
@@ -327,7 +344,9 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv3d_wgrad_params": Conv3dWgradParams, "ucnerf_bn_bwd_reduce_params": BnBwdReduceParams,
                  "ucnerf_bn_bwd_apply_params": BnBwdApplyParams,
                  "ucnerf_conv2d_wgrad_params": Conv2dWgradParams, "ucnerf_conv2d_dgrad_s2_params": Conv2dDgradS2Params,
-                 "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams}
+                 "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams,
+                 "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
+                 "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -428,6 +447,11 @@ SYMBOLS = {
     "ucnerf_conv2d_wgrad": (C.c_int, [_P, _P]),
     "ucnerf_conv2d_dgrad_s2": (C.c_int, [_P, _P]),
     "ucnerf_conv2d_bias_grad": (C.c_int, [_P, _P]),
+    # batch-norm with the statistics kept per group of images: FeatureNet over all views in one pass (additive to ABI v6)
+    "ucnerf_bn_stats_groups": (C.c_int, [_P, _P]),
+    "ucnerf_bn_apply_groups": (C.c_int, [_P, _P]),
+    "ucnerf_bn_bwd_reduce_groups": (C.c_int, [_P, _P]),
+    "ucnerf_bn_bwd_apply_groups": (C.c_int, [_P, _P]),
     # the cascade depth loss on the device (additive to ABI v6)
     "ucnerf_cas_loss_workspace_floats": (C.c_int64, [C.c_int32, _P]),
     "ucnerf_cas_loss_fwd": (C.c_int, [_P, _P]),

@@ -174,11 +174,12 @@ def _conv_weights(module):
     return [m.weight for m in module.modules() if isinstance(m, (nn.Conv2d, nn.Conv3d, nn.ConvTranspose3d))]
 
 
-def _bn_train(layer, y, skip=None):
-    """The layer's batch-norm, ReLU and skip addition in place on its convolution's output, with the batch's own statistics."""
+def _bn_train(layer, y, skip=None, groups=1):
+    """The layer's batch-norm, ReLU and skip addition in place on its convolution's output, with the batch's own statistics (`groups` > 1: those
+    of each group of images)."""
     bn = layer.bn
     return ops.batch_norm_train(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, momentum=bn.momentum, eps=bn.eps,
-                                relu=layer.relu, skip=skip, out=y)
+                                relu=layer.relu, skip=skip, out=y, groups=groups)
 
 
 class FeatureNet(nn.Module):
@@ -191,7 +192,8 @@ class FeatureNet(nn.Module):
     fourth, under train() + grad enabled: the eight batch-normed layers are `ops.conv2d_bn_train`, the five bare ones `ops.conv2d_train`, forward
     and backward on the HIP kernels (csrc/conv2d_bwd.hip), the running statistics moved as torch moves them; the two nearest-neighbour
     upsamplings and additions stay torch operations.  The default "torch" keeps torch's layers there.  The attribute `training_route` exists only
-    on a module built with training="device": one without it trains through torch, as every FeatureNet did before the keyword."""
+    on a module built with training="device": one without it trains through torch, as every FeatureNet did before the keyword.
+    `forward_views` runs the pyramid ONCE over all the views of a sample and gives what the per-view calls give (see there)."""
 
     def __init__(self, base_channels=8, num_stage=3, stride=4, arch_mode="fpn", inference="device", batch_stats="torch", training="torch"):
         super().__init__()
@@ -258,7 +260,31 @@ class FeatureNet(nn.Module):
         outputs["stage3"] = self.out3(intra)
         return outputs
 
-    def _forward_device(self, x, batch_stats=False):
+    def forward_views(self, imgs):
+        """The features of all V views of one sample in ONE pass: imgs [1,V,3,H,W] or [V,3,H,W] -> {"stage1": [V,4c,H/4,W/4], "stage2":
+        [V,2c,H/2,W/2], "stage3": [V,c,H,W]}, view i's rows being what `forward(imgs[:, i])` returns when the views are run one after another in
+        ascending order, the batch-norm buffers left as those V calls leave them.  The route is chosen by `forward`'s own predicates: under
+        eval() + no_grad one folded pass over the V images (already per image); under train() + no_grad with batch_stats="device" the same
+        launches with every batch-norm keeping its statistics per view (`ops.batch_norm_train(..., groups=V)`: outputs and buffers bit for bit
+        the loop's); under train() + grad with training="device" the layer functions on the V-image batch (`ops.conv2d_bn_train(..., groups=V)`:
+        outputs, buffers and the image gradient bit for bit the loop's, the parameter gradients its sums in another order).  Anywhere else --
+        torch's routes, CPU tensors -- it IS the loop, concatenated."""
+        if not torch.is_tensor(imgs) or imgs.dim() not in (4, 5) or (imgs.dim() == 5 and imgs.shape[0] != 1) or imgs.shape[-4] < 1:
+            raise RuntimeError("uc_nerf_amd FeatureNet.forward_views: imgs must be [1,V,3,H,W] or [V,3,H,W] with at least one view, got %s"
+                               % (tuple(imgs.shape) if torch.is_tensor(imgs) else type(imgs),))
+        x = imgs[0] if imgs.dim() == 5 else imgs
+        V = x.shape[0]
+        if _device_route(self, x):
+            return self._forward_device(x)
+        if V <= ops.BN_MAX_GROUPS:
+            if _batch_stats_route(self, x):
+                return self._forward_device(x, batch_stats=True, groups=V)
+            if _training_route(self, x):
+                return self._forward_train(x, groups=V)
+        per_view = [self.forward(x[i:i + 1]) for i in range(V)]
+        return {key: torch.cat([out[key] for out in per_view]) for key in per_view[0]}
+
+    def _forward_device(self, x, batch_stats=False, groups=1):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
             raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
                                "it), got %s" % (tuple(x.shape),))
@@ -273,7 +299,7 @@ class FeatureNet(nn.Module):
                 bias = conv.bias.detach() if conv.bias is not None else folded[i][1]
                 return ops.conv2d_bias_relu(t, folded[i][0], bias, stride=conv.stride[0], pad=conv.padding[0], relu=relu)
             y = ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=False)
-            return _bn_train(layers[i], y)
+            return _bn_train(layers[i], y, groups=groups)
 
         conv0 = run(1, run(0, x, True), True)
         conv1 = run(4, run(3, run(2, conv0, True), True), True)
@@ -285,7 +311,7 @@ class FeatureNet(nn.Module):
         outputs["stage3"] = run(12, intra, False)
         return outputs
 
-    def _forward_train(self, x):
+    def _forward_train(self, x, groups=1):
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
             raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
                                "it), got %s" % (tuple(x.shape),))
@@ -298,7 +324,7 @@ class FeatureNet(nn.Module):
                 conv, bn = layer.conv, layer.bn
                 return ops.conv2d_bn_train(t, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                            momentum=bn.momentum, eps=bn.eps, stride=conv.stride[0], pad=conv.padding[0], relu=layer.relu,
-                                           packed=f[i][0], packed_dgrad=d[i])
+                                           packed=f[i][0], packed_dgrad=d[i], groups=groups)
             return ops.conv2d_train(t, layer.weight, layer.bias, stride=layer.stride[0], pad=layer.padding[0], packed=f[i][0], packed_dgrad=d[i])
 
         conv0 = run(1, run(0, x))
@@ -504,13 +530,19 @@ class CascadeMVSNet(nn.Module):
     depth regression).  grad_method "detach": the previous stage's depth is detached before the next stage's hypotheses are built; "undetach"
     (the other branch of :716-719): it is not, and the hypotheses, the regressed depth and so the earlier stages carry its gradient.  The reference
     takes ANY other string for that branch; here a value that is neither of the two is refused, so that a misspelt "detach" does not silently
-    change what trains."""
+    change what trains.
+    `feature_views`: "loop" (the default, the reference's: `feature` is called once per view) or "batched": `feature.forward_views(imgs)` is
+    called once for all views (FeatureNet's gives the loop's features, see there) and `DepthNet` reads its [V,C,h,w] tensors where they are."""
 
     GRAD_METHODS = ("detach", "undetach")
+    FEATURE_VIEWS = ("loop", "batched")
 
     def __init__(self, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
-                 arch_mode="fpn", cr_base_chs=[8, 8, 8], *, feature=None, cost_regularization=None):
+                 arch_mode="fpn", cr_base_chs=[8, 8, 8], *, feature=None, cost_regularization=None, feature_views="loop"):
         super().__init__()
+        if not isinstance(feature_views, str) or feature_views not in self.FEATURE_VIEWS:
+            raise ValueError("uc_nerf_amd CascadeMVSNet: feature_views=%r -- \"loop\" (the feature net is called once per view) or \"batched\" (its "
+                             "forward_views once for all of them)" % (feature_views,))
         if grad_method not in self.GRAD_METHODS:
             raise NotImplementedError("uc_nerf_amd CascadeMVSNet: grad_method=%r -- \"detach\" (the reference's default: the depth is detached between "
                                       "stages) or \"undetach\" (it stays in the graph)" % (grad_method,))
@@ -528,6 +560,10 @@ class CascadeMVSNet(nn.Module):
         self.stage_infos = {"stage1": {"scale": 4.0}, "stage2": {"scale": 2.0}, "stage3": {"scale": 1.0}}
         if self.num_stage > len(self.stage_infos):
             raise ValueError("uc_nerf_amd CascadeMVSNet: at most %d stages" % len(self.stage_infos))
+        if feature_views == "batched" and not callable(getattr(feature, "forward_views", None)):
+            raise ValueError("uc_nerf_amd CascadeMVSNet: feature_views=\"batched\" needs a feature module with a forward_views(imgs) method (as "
+                             "uc_nerf_amd's FeatureNet has), got %s" % type(feature).__name__)
+        self.feature_views = feature_views
         self.feature = feature
         per_stage = isinstance(cost_regularization, (list, tuple, nn.ModuleList))
         if share_cr:
@@ -543,12 +579,16 @@ class CascadeMVSNet(nn.Module):
 
     @classmethod
     def with_cnns(cls, view_num=11, ndepths=[48, 32, 8], depth_interals_ratio=[4, 2, 1], share_cr=False, grad_method="detach",
-                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch", training="torch", feature_training="torch"):
+                  arch_mode="fpn", cr_base_chs=[8, 8, 8], inference="device", batch_stats="torch", training="torch", feature_training="torch",
+                  feature_views="loop"):
         """The net with its own `FeatureNet` and one `CostRegNet` per stage (mvs_models.py:678-687), so that a reference checkpoint loads and
         runs without the reference's source.  `inference`: the route both kinds of module take under eval() + no_grad ("device" or "torch");
         `batch_stats`: the one they take under train() + no_grad ("torch", or "device" with inference="device"); `training`: the one the
         `CostRegNet`s take under train() + grad enabled ("torch", or "device" with inference="device": forward and backward on the HIP kernels);
-        `feature_training`: the same choice for the `FeatureNet`.  With both "device" a training step stays on the project's kernels end to end."""
+        `feature_training`: the same choice for the `FeatureNet`.  With both "device" a training step stays on the project's kernels end to end.
+        `feature_views`: "loop" or "batched", as in the constructor."""
+        if not isinstance(feature_views, str) or feature_views not in cls.FEATURE_VIEWS:
+            raise ValueError("uc_nerf_amd CascadeMVSNet.with_cnns: feature_views=%r -- \"loop\" or \"batched\"" % (feature_views,))
         if share_cr:
             raise NotImplementedError("uc_nerf_amd CascadeMVSNet.with_cnns: share_cr=True (one regulariser for stages whose feature channels "
                                       "differ; the reference's constructor fails on it too) -- hand a module in through CascadeMVSNet(...)")
@@ -557,7 +597,8 @@ class CascadeMVSNet(nn.Module):
         regs = nn.ModuleList([CostRegNet(in_channels=feature.out_channels[i], base_channels=cr_base_chs[i], inference=inference, batch_stats=batch_stats,
                                          training=training)
                               for i in range(len(ndepths))])
-        return cls(view_num, ndepths, depth_interals_ratio, share_cr, grad_method, arch_mode, cr_base_chs, feature=feature, cost_regularization=regs)
+        return cls(view_num, ndepths, depth_interals_ratio, share_cr, grad_method, arch_mode, cr_base_chs, feature=feature, cost_regularization=regs,
+                   feature_views=feature_views)
 
     def forward(self, imgs, affine_mat, affine_mat_inv, near_far, pad):
         if imgs.shape[0] != 1:
@@ -567,12 +608,16 @@ class CascadeMVSNet(nn.Module):
         # (near, far) on the device: read there by the kernel.  The stage-1 row of the reference, near * (1 - t) + far * t over 48 steps
         # (:694-699), is only ever read at its two ends -- near and far themselves -- so the pair stands for it.
         near_far = torch.cat([_dev_scalar(near_far[0], dev), _dev_scalar(near_far[1], dev)])
-        features = [self.feature(imgs[:, i]) for i in range(imgs.size(1))]
+        if self.feature_views == "batched":
+            batched = self.feature.forward_views(imgs)                                   # {stage: [V,C,h,w]}
+        else:
+            features = [self.feature(imgs[:, i]) for i in range(imgs.size(1))]
         outputs = {}
         depth = None
         for stage_idx in range(self.num_stage):
             key = "stage{}".format(stage_idx + 1)
-            features_stage = [feat[key] for feat in features]
+            # ([V,1,C,h,w] as a view: DepthNet takes a tensor as it is, no torch.stack copy)
+            features_stage = batched[key].unsqueeze(1) if self.feature_views == "batched" else [feat[key] for feat in features]
             scale = int(self.stage_infos[key]["scale"])
             stage_pad = pad if stage_idx == 2 else 0                                     # :735-740
             D = self.ndepths[stage_idx]

@@ -27,7 +27,7 @@ from .mvs import (_CasLoss, _CostVolumeFn, _DepthHypothesesFn, _DepthRegressFn, 
 from .metrics import (PackedConv, _eval_workspace, _is_cell, colormap_table, conv2d_bias_relu, conv2d_pack,  # noqa: F401
                       depth_colormap, depth_eval, depth_minmax, image_eval, image_group_pixels, image_put, lpips_alex,
                       lpips_layer, lpips_workspace_floats, maxpool2d, minmax_reset, minmax_value)
-from .cnn import (PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _Conv2dTrain, _Conv3dBnTrain, _Conv3dTrain, batch_norm_train,  # noqa: F401
+from .cnn import (BN_MAX_GROUPS, PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _Conv2dTrain, _Conv3dBnTrain, _Conv3dTrain, batch_norm_train,  # noqa: F401
                   batch_norm_train_bwd, conv2d_bias_grad, conv2d_bn_train, conv2d_dgrad, conv2d_dgrad_pack, conv2d_train, conv2d_wgrad,
                   conv3d, conv3d_bn_train, conv3d_dgrad, conv3d_dgrad_pack, conv3d_pack, conv3d_train, conv3d_wgrad)
 from .render import RenderPass      # noqa: F401

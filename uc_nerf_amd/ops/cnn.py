@@ -1,7 +1,8 @@
 """The 3-D convolutions of the MVS cost regularisation on the device (csrc/conv3d.hip), the batch-statistic batch-norm of both CNNs (csrc/bn.hip), and
 their backward: the weight gradient (csrc/conv3d_bwd.hip), the input gradient on the forward kernel, the batch-norm backward with the ReLU mask,
 and the differentiable layer CostRegNet's training route is made of.  The same for FeatureNet's 2-D layers: the weight, stride-2 input and bias
-gradients of csrc/conv2d_bwd.hip and the two differentiable layer functions of its training route."""
+gradients of csrc/conv2d_bwd.hip and the two differentiable layer functions of its training route.  `groups=` on the batch-norm functions keeps
+the statistics per group of images (csrc/bn_groups.hip): FeatureNet over all the views of a sample in one pass."""
 import torch
 
 from .. import _lib as L
@@ -74,22 +75,40 @@ def conv3d(x, weight, bias, stride=1, pad=0, relu=True, skip=None, transposed=Fa
     return y
 
 
+BN_MAX_GROUPS = 64                                         # csrc/bn_device.h: BN_MAX_GROUPS
+
+
+def _bn_groups(groups, y, who):
+    """`groups` of the batch-norm functions -> G, checked against the first dimension of y (before anything else is: no device is needed to be told)."""
+    if isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups <= BN_MAX_GROUPS:
+        raise RuntimeError("uc_nerf_amd.%s: groups=%r (an integer from 1 to %d)" % (who, groups, BN_MAX_GROUPS))
+    if groups > 1 and torch.is_tensor(y) and y.dim() >= 1 and y.shape[0] % groups:
+        raise RuntimeError("uc_nerf_amd.%s: groups=%d does not divide the first dimension of %s" % (who, groups, tuple(y.shape)))
+    return groups
+
+
 def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, relu=True, skip=None, out=None,
-                     return_stats=False):
+                     return_stats=False, groups=1):
     """Train-mode batch-norm of y [n,C,*spatial] (float32, contiguous, on the device) with the statistics of the batch itself, forward only
     (csrc/bn.hip: `ucnerf_bn_stats` then `ucnerf_bn_apply`, the order of every sum fixed, nothing read back): out = act((y - mean) / sqrt(var +
     eps) * weight + bias) (+ skip), var the biased variance, act ReLU with `relu`, `skip` added AFTER the activation.  `running_mean`,
     `running_var` (float32 [C]) and `num_batches_tracked` (one int64) move in place as nn.BatchNorm moves them (the unbiased variance, momentum a
     float in (0, 1]); their version counters are bumped, since the kernels write through raw pointers.  `out`: a tensor like y to write into, y
-    itself for in place.  -> out, or (out, saved_mean, saved_var) with `return_stats`.  No autograd: inputs that require grad are used detached."""
+    itself for in place.  -> out, or (out, saved_mean, saved_var) with `return_stats`.  No autograd: inputs that require grad are used detached.
+    `groups` = G > 1 (csrc/bn_groups.hip, the same two launches): the first dimension is G groups of n / G consecutive images, each normalised
+    with its OWN statistics, bit for bit what G calls on the G slabs give, the running statistics moved G times in ascending group order;
+    saved_mean and saved_var then are [G,C]."""
     if torch.is_tensor(y) and y.dim() >= 2 and 0 < y.numel() == y.shape[1]:     # n S == 1: torch's own refusal, before anything else is looked at
         raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(y.size()))
+    G = _bn_groups(groups, y, "batch_norm_train")
+    if G > 1 and torch.is_tensor(y) and y.dim() >= 2 and 0 < y.numel() == G * y.shape[1]:      # ... and the one each of the G calls would meet
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(torch.Size((y.shape[0] // G,) + tuple(y.shape[1:]))))
     if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32 and y.dim() >= 2 and y.is_contiguous() and y.numel() > 0):
         raise RuntimeError("uc_nerf_amd.batch_norm_train: y must be a non-empty contiguous float32 [n,C,*spatial] tensor on a ROCm device, got %s"
                            % ("%s %s on %s" % (tuple(y.shape), y.dtype, y.device) if torch.is_tensor(y) else type(y)))
     given, y = out, y.detach()
-    n, C = y.shape[0], y.shape[1]
-    S = y.numel() // (n * C)
+    n, C = y.shape[0] // G, y.shape[1]
+    S = y.numel() // (G * n * C)
     if momentum is None or not 0.0 < float(momentum) <= 1.0 or not float(eps) > 0.0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train: momentum=%r eps=%r (a float momentum in (0, 1], a positive eps)" % (momentum, eps))
     per_channel = []
@@ -111,17 +130,19 @@ def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tra
     if P < 0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
                            % (tuple(y.shape),))
-    workspace = torch.empty((C, P, 3), dtype=torch.float64, device=y.device)
-    saved = torch.empty((2, C), device=y.device)
-    s = L.BnStatsParams()
-    s.n, s.C, s.S, s.workspace_triples, s.y, s.workspace = n, C, S, C * P, _ptr(y), _ptr(workspace)
-    _launch("ucnerf_bn_stats", s, y.device)
-    a = L.BnApplyParams()
-    a.n, a.C, a.S, a.workspace_triples, a.eps, a.momentum, a.relu = n, C, S, C * P, float(eps), float(momentum), int(bool(relu))
+    workspace = torch.empty((G, C, P, 3) if G > 1 else (C, P, 3), dtype=torch.float64, device=y.device)
+    saved = torch.empty((2, G, C) if G > 1 else (2, C), device=y.device)
+    s = L.BnStatsGroupsParams() if G > 1 else L.BnStatsParams()
+    a = L.BnApplyGroupsParams() if G > 1 else L.BnApplyParams()
+    if G > 1:
+        s.G = a.G = G
+    s.n, s.C, s.S, s.workspace_triples, s.y, s.workspace = n, C, S, G * C * P, _ptr(y), _ptr(workspace)
+    _launch("ucnerf_bn_stats_groups" if G > 1 else "ucnerf_bn_stats", s, y.device)
+    a.n, a.C, a.S, a.workspace_triples, a.eps, a.momentum, a.relu = n, C, S, G * C * P, float(eps), float(momentum), int(bool(relu))
     a.y, a.workspace, a.weight, a.bias, a.skip, a.out = _ptr(y), _ptr(workspace), _ptr(weight), _ptr(bias), _ptr(skip), _ptr(out)
     a.saved_mean, a.saved_var, a.running_mean, a.running_var = _ptr(saved[0]), _ptr(saved[1]), _ptr(running_mean), _ptr(running_var)
     a.num_batches_tracked = _ptr(nbt)
-    _launch("ucnerf_bn_apply", a, y.device)
+    _launch("ucnerf_bn_apply_groups" if G > 1 else "ucnerf_bn_apply", a, y.device)
     for t in (running_mean, running_var, nbt):
         torch.autograd.graph.increment_version(t)
     if given is not None:
@@ -210,25 +231,29 @@ def conv3d_dgrad(grad_y, weight, x_shape, stride=1, pad=1, transposed=False):
     return conv3d(grad_y, w, zero, relu=False, skip=None, **route)
 
 
-def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1e-5, relu=True, out=None):
+def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1e-5, relu=True, out=None, groups=1):
     """The backward of `batch_norm_train` (csrc/bn.hip: `ucnerf_bn_bwd_reduce` then `ucnerf_bn_bwd_apply`, float64 sums in a fixed order, nothing
     read back): grad_out the gradient of act(bn(y)), y the tensor the forward normalised, saved_mean / saved_var what it returned with
     `return_stats`; the ReLU's mask is recomputed from y bit for bit.  `out`: a tensor like y for grad_y, grad_out itself for in place.
-    -> (grad_y, grad_weight, grad_bias).  The skip's gradient is grad_out itself."""
+    -> (grad_y, grad_weight, grad_bias).  The skip's gradient is grad_out itself.
+    `groups` = G > 1 (csrc/bn_groups.hip), as in the forward: saved_mean / saved_var are its [G,C]; grad_y is, group by group, the ungrouped
+    backward's bit for bit; grad_weight and grad_bias [C] are the sums over the groups, added in float64 and rounded once."""
+    G = _bn_groups(groups, y, "batch_norm_train_bwd")
     for t, name in ((grad_out, "grad_out"), (y, "y")):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.is_contiguous() and t.numel() > 0):
             raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a non-empty contiguous float32 [n,C,*spatial] tensor on a ROCm device" % name)
     if grad_out.shape != y.shape or grad_out.device != y.device:
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: grad_out %s and y %s differ" % (tuple(grad_out.shape), tuple(y.shape)))
     grad_out, y = grad_out.detach(), y.detach()
-    n, C = y.shape[0], y.shape[1]
-    S = y.numel() // (n * C)
+    n, C = y.shape[0] // G, y.shape[1]
+    S = y.numel() // (G * n * C)
     if not float(eps) > 0.0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: eps=%r (a positive float)" % (eps,))
     per_channel = []
     for t, name in ((saved_mean, "saved_mean"), (saved_var, "saved_var"), (weight, "weight"), (bias, "bias")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == (C,) and t.is_contiguous()):
-            raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a contiguous float32 [%d] tensor on y's device" % (name, C))
+        want = (G, C) if G > 1 and name.startswith("saved_") else (C,)
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == want and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a contiguous float32 %s tensor on y's device" % (name, list(want)))
         per_channel.append(t.detach())
     if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == y.device and out.shape == y.shape and out.is_contiguous()):
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: out must be a contiguous float32 tensor of y's shape %s on its device" % (tuple(y.shape),))
@@ -237,17 +262,19 @@ def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
                            % (tuple(y.shape),))
     grad_y = torch.empty_like(y) if out is None else out.detach()
-    workspace = torch.empty((C, P, 2), dtype=torch.float64, device=y.device)
+    workspace = torch.empty((G, C, P, 2) if G > 1 else (C, P, 2), dtype=torch.float64, device=y.device)
     grads = torch.empty((2, C), device=y.device)
-    r = L.BnBwdReduceParams()
-    a = L.BnBwdApplyParams()
+    r = L.BnBwdReduceGroupsParams() if G > 1 else L.BnBwdReduceParams()
+    a = L.BnBwdApplyGroupsParams() if G > 1 else L.BnBwdApplyParams()
     for q in (r, a):
-        q.n, q.C, q.S, q.workspace_pairs, q.eps, q.relu = n, C, S, C * P, float(eps), int(bool(relu))
+        if G > 1:
+            q.G = G
+        q.n, q.C, q.S, q.workspace_pairs, q.eps, q.relu = n, C, S, G * C * P, float(eps), int(bool(relu))
         q.g, q.y, q.workspace = _ptr(grad_out), _ptr(y), _ptr(workspace)
         q.saved_mean, q.saved_var, q.weight, q.bias = (_ptr(t) for t in per_channel)
     a.grad_y, a.grad_weight, a.grad_bias = _ptr(grad_y), _ptr(grads[0]), _ptr(grads[1])
-    _launch("ucnerf_bn_bwd_reduce", r, y.device)
-    _launch("ucnerf_bn_bwd_apply", a, y.device)
+    _launch("ucnerf_bn_bwd_reduce_groups" if G > 1 else "ucnerf_bn_bwd_reduce", r, y.device)
+    _launch("ucnerf_bn_bwd_apply_groups" if G > 1 else "ucnerf_bn_bwd_apply", a, y.device)
     return (grad_y if out is None else out), grads[0], grads[1]
 
 
@@ -441,13 +468,13 @@ class _Conv2dBnTrain(torch.autograd.Function):
     as of the forward."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, buffers, momentum, eps, stride, pad, relu, packed, packed_dgrad):
+    def forward(ctx, x, weight, gamma, beta, buffers, momentum, eps, stride, pad, relu, packed, packed_dgrad, groups):
         running_mean, running_var, nbt = buffers
         w = packed if packed is not None else conv2d_pack(weight)
         y = conv2d_bias_relu(x, w, torch.zeros(w.cout, device=x.device), stride=stride, pad=pad, relu=False)
         out, mean, var = batch_norm_train(y, gamma, beta, running_mean, running_var, nbt, momentum=momentum, eps=eps, relu=relu, skip=None, out=None,
-                                          return_stats=True)
-        ctx.layer = (w.K, stride, pad, bool(relu), float(eps), tuple(x.shape))
+                                          return_stats=True, groups=groups)
+        ctx.layer = (w.K, stride, pad, bool(relu), float(eps), tuple(x.shape), groups)
         ctx.packed_dgrad = None
         if ctx.needs_input_grad[0]:
             ctx.packed_dgrad = packed_dgrad if packed_dgrad is not None else conv2d_dgrad_pack(weight, stride, pad)
@@ -458,11 +485,11 @@ class _Conv2dBnTrain(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         x, y, mean, var, gamma, beta = ctx.saved_tensors
-        K, stride, pad, relu, eps, x_shape = ctx.layer
-        grad_y, grad_gamma, grad_beta = batch_norm_train_bwd(grad_out.contiguous(), y, mean, var, gamma, beta, eps=eps, relu=relu)
+        K, stride, pad, relu, eps, x_shape, groups = ctx.layer
+        grad_y, grad_gamma, grad_beta = batch_norm_train_bwd(grad_out.contiguous(), y, mean, var, gamma, beta, eps=eps, relu=relu, groups=groups)
         grad_w = conv2d_wgrad(x, grad_y, K, stride, pad) if ctx.needs_input_grad[1] else None
         grad_x = conv2d_dgrad(grad_y, ctx.packed_dgrad, x_shape, stride, pad) if ctx.needs_input_grad[0] else None
-        return (grad_x, grad_w, grad_gamma if ctx.needs_input_grad[2] else None, grad_beta if ctx.needs_input_grad[3] else None) + (None,) * 8
+        return (grad_x, grad_w, grad_gamma if ctx.needs_input_grad[2] else None, grad_beta if ctx.needs_input_grad[3] else None) + (None,) * 9
 
 
 class _Conv2dTrain(torch.autograd.Function):
@@ -501,17 +528,19 @@ def _train_weight2d(weight, stride, pad, who):
 
 
 def conv2d_bn_train(x, weight, bn_weight, bn_bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, stride=1, pad=1, relu=True,
-                    packed=None, packed_dgrad=None):
+                    packed=None, packed_dgrad=None, groups=1):
     """act(batch_norm(conv2d(x, weight))) with the batch's own statistics, DIFFERENTIABLE (once) in x, weight, bn_weight and bn_bias, forward and
     backward on the device: `conv2d_bias_relu` and `batch_norm_train` (the running statistics move exactly as there), then
     `batch_norm_train_bwd`, `conv2d_wgrad` (only if the weight needs a gradient) and `conv2d_dgrad` (only if x does).  K 1, 3 or 5 with pad
     (K - 1) / 2, stride 1, or 2 with K 3 or 5 (even sizes).  `packed` / `packed_dgrad`: what `conv2d_pack(weight)` / `conv2d_dgrad_pack(weight,
     stride, pad)` made of the weight AS IT IS NOW (a module's cache); without them the weight is prepared here.  Either way the backward uses the
-    weight's values as of this call, whatever happens to the tensor afterwards."""
+    weight's values as of this call, whatever happens to the tensor afterwards.  `groups` = G > 1: x is G groups of n / G consecutive images and the
+    batch-norm keeps its statistics per group (`batch_norm_train`'s `groups`); the convolution and its gradients are per image anyway."""
+    groups = _bn_groups(groups, x, "conv2d_bn_train")
     _dev(x)
     _train_weight2d(weight, int(stride), int(pad), "conv2d_bn_train")
     return _Conv2dBnTrain.apply(x, weight, bn_weight, bn_bias, (running_mean, running_var, num_batches_tracked), momentum, float(eps), int(stride), int(pad),
-                                bool(relu), packed, packed_dgrad)
+                                bool(relu), packed, packed_dgrad, groups)
 
 
 def conv2d_train(x, weight, bias=None, stride=1, pad=0, packed=None, packed_dgrad=None):
