@@ -1184,6 +1184,83 @@ typedef struct ucnerf_depth_colormap_params ucnerf_depth_colormap_params;
 int ucnerf_depth_colormap(const ucnerf_depth_colormap_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * d1   one training / validation sample out of a scene that is resident on the device -- data/scared.py:387-522 (ScaredDataset.__getitem__: PIL,
+ *      ToTensor, Normalize, four cv2 resizes, 3 V projection matrices and their inverses, a shuffled keypoint list, then the DataLoader's collation
+ *      and a host-to-device copy) and train.py:61-70 (unpreprocess).  Everything that is constant per FRAME is computed once on the host with the
+ *      reference's own calls and uploaded (uc_nerf_amd/data/scene.py); what is left per SAMPLE is this one launch.  (Added to ABI v6; nothing above
+ *      moved.  Struct declared with a tag: mirrored in _lib.ADDED_STRUCTS.)  The entry point does not synchronise the stream and reads nothing
+ *      back; all stores are plain vector stores.
+ *
+ *   Resident inputs (N frames of H x W pixels):
+ *     frames       uint8, frame f at byte f * frame_stride, [H,W,3] interleaved; frame_stride >= 3 H W and a multiple of 4, the array itself 4-byte
+ *                  aligned and frame_stride * N bytes long (the bytes are read as whole dwords, four pixels = three dwords per thread)
+ *     depth_img, weight_img   [N,H,W]   the sparse depth map and the normalised weight map
+ *     row1, col1, row2, col2  int32 [h1], [w1], [h2], [w2]: source row / column of every row / column of the two nearest-neighbour pyramid levels
+ *     kp_depth, kp_weight [K], kp_coord int32 [K,2] = (h, w): the keypoint lists of all frames, concatenated; the target's are kp_first .. + n_kp - 1
+ *     c2w, w2c [N,4,4]; intrinsic [N,3,3]; affine, affine_inv [N,3,4,4]; ref_proj_inv [N,4,4]
+ *   view_ids[0] is the target, view_ids[1 .. V-1] the sources (the target may be among them).  With f = view_ids[v]:
+ *     images[v][c][q]       = ((float(u) / 255.0f) - mean[c]) / std[c],  u = frames[f][q][c]: an IEEE division (ToTensor), a float32 subtraction and
+ *                             a second IEEE division (Normalize's sub_().div_()); three roundings, nothing contracted, no reciprocal multiply
+ *     images_unpre[v][c][q] = (images[v][c][q] - unpre_mean[c]) / unpre_std[c], the same way (images_unpre may be NULL: not written)
+ *     sd1[y][x] = depth_img[target][row1[y]][col1[x]], sd2 with row2 / col2; wt1, wt2 the same from weight_img
+ *     rays_depth[i] = [[d, d, d], [w, w, w], [h, w_, 1]] of keypoint kp_first + perm[i], i < n_rows: what the reference's concatenate gives,
+ *                     [n,3,3] (its comment says 4 x 3; the code makes three rows).  A perm[i] outside 0 .. n_kp - 1 reads nothing: the row is NaN.
+ *     c2ws, w2cs, intrinsics, affine_mat, affine_mat_inv: the rows of frame f;  near_fars[v] = (near, far);  view_ids_out[v] = f (int64)
+ *     proj_mats[0] = the first three rows of the identity;  proj_mats[v] = (affine[f][2] @ ref_proj_inv[target])[:3] for v >= 1, element (r, c) =
+ *                     fmaf(a[r][3], b[3][c], fmaf(a[r][2], b[2][c], fmaf(a[r][1], b[1][c], a[r][0] * b[0][c]))): k = 0 .. 3 in ascending order
+ *                     from a first product (torch.matmul's order is the BLAS's; this one is fixed)
+ *   UCNERF_EINVAL, checked on the host before anything is launched: a negative count or size, H W > 2^24, V outside 1..9, a view id outside
+ *   0 .. N-1, n_rows > 1024 or n_rows > n_kp, a keypoint segment that overruns kp_total, a pyramid level larger than the image, frame_stride too small or not a multiple of 4, a NULL
+ *   required pointer (kp_* and perm are required only when n_rows > 0; images_unpre is optional).  n_rows == 0 is legal: a frame without keypoints
+ *   gives an empty rays_depth.  Bound: latency (V H W 3 bytes in, 4 to 8 times that out: a few microseconds of traffic). */
+struct ucnerf_sample_assemble_params {
+    int32_t N, H, W, V;
+    int32_t h1, w1, h2, w2;    /* pyramid levels: (H / 4, W / 4) and (H / 2, W / 2) in the reference */
+    int32_t frame_stride;      /* bytes between frames */
+    int32_t kp_total;          /* K: keypoints of all frames */
+    int32_t kp_first, n_kp;    /* the target's segment of the keypoint lists: kp_first + n_kp <= kp_total */
+    int32_t n_rows;            /* rows of rays_depth: min(n_kp, 1024) in the reference */
+    int32_t view_ids[9];
+    float mean[3], std[3];     /* Normalize's */
+    float unpre_mean[3], unpre_std[3];
+    float near_far[2];
+    const uint8_t* frames;
+    const float* depth_img;
+    const float* weight_img;
+    const int32_t* row1;
+    const int32_t* col1;
+    const int32_t* row2;
+    const int32_t* col2;
+    const float* kp_depth;
+    const float* kp_weight;
+    const int32_t* kp_coord;
+    const int32_t* perm;       /* [>= n_rows] distinct indices below n_kp */
+    const float* c2w;
+    const float* w2c;
+    const float* intrinsic;
+    const float* affine;
+    const float* affine_inv;
+    const float* ref_proj_inv;
+    float* images;             /* [V,3,H,W] */
+    float* images_unpre;       /* [V,3,H,W], or NULL */
+    float* sd1;                /* [h1,w1] */
+    float* sd2;                /* [h2,w2] */
+    float* wt1;
+    float* wt2;
+    float* rays_depth;         /* [n_rows,3,3] */
+    float* c2ws;               /* [V,4,4] */
+    float* w2cs;
+    float* intrinsics;         /* [V,3,3] */
+    float* affine_mat;         /* [V,3,4,4] */
+    float* affine_mat_inv;
+    float* proj_mats;          /* [V,3,4] */
+    float* near_fars;          /* [V,2] */
+    int64_t* view_ids_out;     /* [V] */
+};
+typedef struct ucnerf_sample_assemble_params ucnerf_sample_assemble_params;
+int ucnerf_sample_assemble(const ucnerf_sample_assemble_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3   the cascade depth loss on the device -- network/mvs_models.py:512-529 (cas_mvsnet_loss) without its boolean-mask indexing: est[mask],
  *      gt[mask] and w[w > 0] compact, compaction needs the element counts on the host, and a step that reads the device back cannot be captured
  *      into a graph.  Here the counts stay on the device.  (Added to ABI v6; nothing above moved.  Structs declared with a tag: mirrored in

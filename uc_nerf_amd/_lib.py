@@ -292,6 +292,16 @@ class DepthColormapParams(C.Structure):
     _fields_ = [("count", i32), ("range_host", C.c_double * 2), ("depth", vp), ("minmax", vp), ("table", vp), ("index", vp), ("color", vp)]
 
 
+class SampleAssembleParams(C.Structure):
+    _fields_ = [("N", i32), ("H", i32), ("W", i32), ("V", i32), ("h1", i32), ("w1", i32), ("h2", i32), ("w2", i32), ("frame_stride", i32),
+                ("kp_total", i32), ("kp_first", i32), ("n_kp", i32), ("n_rows", i32), ("view_ids", i32 * 9), ("mean", f32 * 3), ("std", f32 * 3),
+                ("unpre_mean", f32 * 3), ("unpre_std", f32 * 3), ("near_far", f32 * 2), ("frames", vp), ("depth_img", vp), ("weight_img", vp),
+                ("row1", vp), ("col1", vp), ("row2", vp), ("col2", vp), ("kp_depth", vp), ("kp_weight", vp), ("kp_coord", vp), ("perm", vp),
+                ("c2w", vp), ("w2c", vp), ("intrinsic", vp), ("affine", vp), ("affine_inv", vp), ("ref_proj_inv", vp), ("images", vp),
+                ("images_unpre", vp), ("sd1", vp), ("sd2", vp), ("wt1", vp), ("wt2", vp), ("rays_depth", vp), ("c2ws", vp), ("w2cs", vp),
+                ("intrinsics", vp), ("affine_mat", vp), ("affine_mat_inv", vp), ("proj_mats", vp), ("near_fars", vp), ("view_ids_out", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -346,7 +356,8 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv2d_wgrad_params": Conv2dWgradParams, "ucnerf_conv2d_dgrad_s2_params": Conv2dDgradS2Params,
                  "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams,
                  "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
-                 "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams}
+                 "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams,
+                 "ucnerf_sample_assemble_params": SampleAssembleParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -463,6 +474,8 @@ SYMBOLS = {
     "ucnerf_image_put": (C.c_int, [_P, _P]),
     "ucnerf_depth_minmax": (C.c_int, [_P, _P]),
     "ucnerf_depth_colormap": (C.c_int, [_P, _P]),
+    # one sample of the dataset out of a device-resident scene (additive to ABI v6)
+    "ucnerf_sample_assemble": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

@@ -1,0 +1,102 @@
+"""The input side on the device: one sample of the reference's dataset assembled from a resident scene in one launch."""
+import torch
+
+from .. import _lib as L
+from ._core import _launch, _ptr
+
+SAMPLE_MAX_ROWS = 1024      # the reference's rays_depth[:1024]
+SAMPLE_MAX_VIEWS = 9        # the MLP's view_num range
+
+_RESIDENT = ("frames", "depth_img", "weight_img", "row1", "col1", "row2", "col2", "kp_depth", "kp_weight", "kp_coord",
+             "c2w", "w2c", "intrinsic", "affine", "affine_inv", "ref_proj_inv")
+_RESIDENT_DTYPES = {"frames": torch.uint8, "row1": torch.int32, "col1": torch.int32, "row2": torch.int32, "col2": torch.int32, "kp_coord": torch.int32}
+
+
+def _sample_params(res):
+    """The parameter struct of a resident scene, filled once with everything that does not change between samples (kept on `res`)."""
+    p = getattr(res, "_sample_params", None)
+    if p is not None:
+        return p
+    dev = res.frames.device
+    if dev.type != "cuda":
+        raise RuntimeError("uc_nerf_amd.sample_assemble: the scene must be resident on a ROCm device, it is on %s (there is no host route)" % dev)
+    for name in _RESIDENT:
+        t = getattr(res, name)
+        want = _RESIDENT_DTYPES.get(name, torch.float32)
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == want and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.sample_assemble: resident array %s must be a contiguous %s tensor on %s" % (name, want, dev))
+    N, H, W = int(res.N), int(res.H), int(res.W)
+    if res.frames.dim() != 2 or res.frames.shape[0] != N or res.depth_img.shape != (N, H, W) or res.weight_img.shape != (N, H, W):
+        raise RuntimeError("uc_nerf_amd.sample_assemble: frames must be [N, frame_stride] bytes and the maps [N,H,W]")
+    for name, per in (("c2w", 16), ("w2c", 16), ("intrinsic", 9), ("affine", 48), ("affine_inv", 48), ("ref_proj_inv", 16)):
+        if getattr(res, name).numel() != N * per:
+            raise RuntimeError("uc_nerf_amd.sample_assemble: %s must hold %d floats per frame" % (name, per))
+    K = res.kp_depth.numel()
+    if res.kp_weight.numel() != K or res.kp_coord.numel() != 2 * K or len(res.offsets) != N + 1 or res.offsets[-1] != K:
+        raise RuntimeError("uc_nerf_amd.sample_assemble: the keypoint lists and their offsets disagree")
+    p = L.SampleAssembleParams()
+    p.N, p.H, p.W, p.frame_stride, p.kp_total = N, H, W, res.frames.shape[1], K
+    p.h1, p.w1, p.h2, p.w2 = res.row1.numel(), res.col1.numel(), res.row2.numel(), res.col2.numel()
+    for k in range(3):
+        p.mean[k], p.std[k], p.unpre_mean[k], p.unpre_std[k] = res.mean[k], res.std[k], res.unpre_mean[k], res.unpre_std[k]
+    p.near_far[0], p.near_far[1] = res.near_far
+    for name in _RESIDENT:
+        setattr(p, name, _ptr(getattr(res, name)))
+    res._sample_params = p
+    return p
+
+
+def _carve(sizes):
+    """Offsets (in floats, each a multiple of 4: 16-byte aligned planes, an 8-byte aligned int64 run) of consecutive segments, and the total."""
+    at, offs = 0, []
+    for n in sizes:
+        offs.append(at)
+        at += (n + 3) // 4 * 4
+    return offs, at
+
+
+def sample_assemble(res, view_ids, perm, n_rows, unpreprocess=False):
+    """One sample out of a resident scene (`uc_nerf_amd.data.DeviceScene` holds one): ucnerf_sample_assemble, one launch on the current stream,
+    nothing synchronised or read back.  `res` carries the resident device tensors (frames [N, frame_stride] uint8, depth_img / weight_img [N,H,W],
+    the four int32 index maps, the concatenated keypoint lists with their host `offsets`, the per-frame matrices) and the host constants
+    (mean, std, unpre_mean, unpre_std, near_far).  view_ids: Python ints, the target first.  perm: int32 device tensor of at least `n_rows`
+    distinct indices below the target's keypoint count (not read when n_rows == 0; may then be None).
+    Returns a dict of float32 device tensors with the batch-of-one shapes of the reference's DataLoader: images [1,V,3,H,W] (and images_unpre),
+    sd1 / wt1 [1,h1,w1], sd2 / wt2 [1,h2,w2], rays_depth [1,n_rows,3,3], c2ws / w2cs [1,V,4,4], intrinsics [1,V,3,3], affine_mat / affine_mat_inv
+    [1,V,3,4,4], proj_mats [1,V,3,4], near_fars [1,1,V,2], view_ids [1,V] int64.  All of them are views of one allocation."""
+    p = _sample_params(res)
+    dev = res.frames.device
+    V = len(view_ids)
+    if not 1 <= V <= SAMPLE_MAX_VIEWS:
+        raise RuntimeError("uc_nerf_amd.sample_assemble: %d views, expected 1..%d" % (V, SAMPLE_MAX_VIEWS))
+    n_rows = int(n_rows)
+    if n_rows > 0:
+        if not (torch.is_tensor(perm) and perm.device == dev and perm.dtype == torch.int32 and perm.is_contiguous() and perm.numel() >= n_rows):
+            raise RuntimeError("uc_nerf_amd.sample_assemble: perm must be a contiguous int32 tensor of at least %d indices on %s" % (n_rows, dev))
+    H, W, HW = p.H, p.W, p.H * p.W
+    n1, n2 = p.h1 * p.w1, p.h2 * p.w2
+    img = V * 3 * HW
+    sizes = [img, img if unpreprocess else 0, n1, n2, n1, n2, n_rows * 9, V * 16, V * 16, V * 9, V * 48, V * 48, V * 12, V * 2, V * 2]
+    offs, total = _carve(sizes)
+    buf = torch.empty(total, dtype=torch.float32, device=dev)
+    seg = [buf[o:o + n] for o, n in zip(offs, sizes)]
+    target = int(view_ids[0])
+    p.V, p.n_rows = V, n_rows
+    for v in range(SAMPLE_MAX_VIEWS):
+        p.view_ids[v] = int(view_ids[v]) if v < V else 0
+    if 0 <= target < p.N:                                        # (anything else is refused by the library's own check, with its message)
+        p.kp_first, p.n_kp = int(res.offsets[target]), int(res.offsets[target + 1] - res.offsets[target])
+    else:
+        p.kp_first, p.n_kp = 0, 0
+    p.perm = _ptr(perm) if n_rows > 0 else 0
+    base = buf.data_ptr()
+    (p.images, p.images_unpre, p.sd1, p.sd2, p.wt1, p.wt2, p.rays_depth, p.c2ws, p.w2cs, p.intrinsics, p.affine_mat, p.affine_mat_inv, p.proj_mats,
+     p.near_fars, p.view_ids_out) = [base + 4 * o if n else 0 for o, n in zip(offs, sizes)]
+    _launch("ucnerf_sample_assemble", p, dev)
+    out = dict(images=seg[0].view(1, V, 3, H, W), sd1=seg[2].view(1, p.h1, p.w1), sd2=seg[3].view(1, p.h2, p.w2), wt1=seg[4].view(1, p.h1, p.w1),
+               wt2=seg[5].view(1, p.h2, p.w2), rays_depth=seg[6].view(1, n_rows, 3, 3), c2ws=seg[7].view(1, V, 4, 4), w2cs=seg[8].view(1, V, 4, 4),
+               intrinsics=seg[9].view(1, V, 3, 3), affine_mat=seg[10].view(1, V, 3, 4, 4), affine_mat_inv=seg[11].view(1, V, 3, 4, 4),
+               proj_mats=seg[12].view(1, V, 3, 4), near_fars=seg[13].view(1, 1, V, 2), view_ids=seg[14].view(torch.int64).view(1, V))
+    if unpreprocess:
+        out["images_unpre"] = seg[1].view(1, V, 3, H, W)
+    return out
