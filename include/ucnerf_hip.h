@@ -710,6 +710,11 @@ int ucnerf_depth_regress_bwd(const ucnerf_depth_regress_bwd_params* p, void* str
  *     s_d(Y, X) = mn + d * (mx - mn) / (D - 1)
  *     out[d, y + pad, x + pad] = bilinear sample of s_d at (y, x) of the h x w grid; the border of `pad` pixels repeats the edge value.
  *     Sizes: h0 <= H, w0 <= W, h <= H, w <= W (any ratio, integer or not).
+ *     Non-finite depths land where torch's own ops put them: max / min are torch.clamp's, so a NaN c gives NaN mn and mx (not the full band
+ *     [near, far]); every tap is multiplied by its weight, a zero weight included (0 * NaN = 0 * inf = NaN); and the depth axis has the taps d and
+ *     min(d + 1, D - 1) with the weights 1 and 0, as an interpolation that keeps a size has in torch: out[d] is NaN where a tap of plane d or
+ *     of the next plane is not finite.  No finite value depends on any of this.  (The backward: both pass_lo and pass_hi are 0 on a NaN c, as in
+ *     torch's clamp backward, so a finite g_out gives a finite g_cur_depth whatever cur_depth holds.)
  *   ROW mode (row given; stage 1): mn = row[0], mx = row[D_in - 1], the same s_d for every pixel; H, W, h0, w0, k, near_far, interval are not read.
  * Exactly one of cur_depth / row is non-NULL.  near and far are read on the device (near_far[0], near_far[1]): no host copy of a device
  * value on this path.  D >= 2.  An output of zero elements (h + 2 pad == 0 or w + 2 pad == 0) is success, nothing launched.  Backward (map mode, into

@@ -74,15 +74,25 @@ __global__ void __launch_bounds__(DH_BLOCK) depth_hypotheses_kernel(ucnerf_depth
             const float* r1 = p.cur_depth + (size_t)uy[a].i1 * p.w0;
             const float c = uy[a].l0 * (ux[b].l0 * r0[ux[b].i0] + ux[b].l1 * r0[ux[b].i1])
                           + uy[a].l1 * (ux[b].l0 * r1[ux[b].i0] + ux[b].l1 * r1[ux[b].i1]);
-            const float lo = fmaxf(c - half, near), hi = fminf(c + half, far);      // :540-541
+            // :540-541, torch.clamp: a NaN c stays NaN (fmaxf / fminf would hand back near and far: the full band where the depth is unknown)
+            const float below = c - half, above = c + half;
+            const float lo = below < near ? near : below, hi = above > far ? far : above;
             mn[a][b] = lo;
             interval[a][b] = (hi - lo) / steps;                                      // :544
         }
-    for (int d = d_begin; d < d_end; ++d, out += plane) {
+    auto plane_value = [&](int d) {
         const float fd = (float)d;
         const float s00 = mn[0][0] + fd * interval[0][0], s01 = mn[0][1] + fd * interval[0][1];      // :546-549
         const float s10 = mn[1][0] + fd * interval[1][0], s11 = mn[1][1] + fd * interval[1][1];
-        *out = ty.l0 * (tx.l0 * s00 + tx.l1 * s01) + ty.l1 * (tx.l0 * s10 + tx.l1 * s11);
+        return ty.l0 * (tx.l0 * s00 + tx.l1 * s01) + ty.l1 * (tx.l0 * s10 + tx.l1 * s11);
+    };
+    // the reference's trilinear interpolation keeps the depth axis' size: its taps there are d and min(d + 1, D - 1) with the weights 1 and 0.
+    // The zero-weight tap changes no finite value and turns an infinite next plane into NaN (0 * inf), as torch does
+    float v = plane_value(d_begin);
+    for (int d = d_begin; d < d_end; ++d, out += plane) {
+        const float next = plane_value(min(d + 1, p.D - 1));
+        *out = v + 0.f * next;
+        v = next;
     }
 }
 
