@@ -975,6 +975,9 @@ int ucnerf_conv3d(const ucnerf_conv3d_params* p, void* stream);
  * y is a contiguous float32 [n, C, S] tensor, S the product of the spatial sizes; a channel has N = n S values, numbered i = img * S + offset.
  * Two launches, ucnerf_bn_stats then ucnerf_bn_apply, on one stream; nothing is read back, no atomics, every store a plain vector store: two
  * calls give the same bits, and the pair can sit inside a captured graph.
+ * ONE CODE PATH (csrc/bn.hip): these entry points and the two backward ones below ARE G = 1 of the grouped entry points at the end of this header --
+ * the struct is copied behind G = 1 and the same checks and the same four kernels run; only the name in front of an error text differs
+ * (so a workspace that is too small is now reported as "G C P = 1 x C x P" where these entries used to say "C P = C x P").
  *
  * ucnerf_bn_partials(n, S) = P = min(32, ceil(N / 4096)), the partial slots per channel; < 0 on a bad argument (n or S < 1, N < 2 or above the
  *   limit below).  Pure host.  Slice j of a channel is the values [j L, min((j + 1) L, N)) with L = ceil(N / P) rounded up to a multiple of 4;
@@ -1579,11 +1582,13 @@ int ucnerf_conv2d_bias_grad(const ucnerf_conv2d_bias_grad_params* p, void* strea
  *
  * CONTRACT: for every group the values computed are those the ungrouped pair computes on that group's [n,C,S] slab alone, BIT FOR BIT: the same
  *   P = ucnerf_bn_partials(n, S) and the same slices, the same thread / lane / wave / slice merge order in float64, the same single roundings, the
- *   same float32 fma(y - mu, s, bias) with IEEE division and square root (both files run the same device functions, csrc/bn_device.h).
- *   G == 1 gives the ungrouped entry points' bits in every output.
+ *   same float32 fma(y - mu, s, bias) with IEEE division and square root.  There is one code path (csrc/bn.hip, four kernels with the group on
+ *   the grid's third dimension): the ungrouped entry points copy their struct behind G = 1 and call what these call, so G == 1 IS the ungrouped
+ *   entry points in every output, and what a group computes does not depend on G.
  * Workspaces: [G,C,P,3] float64 for the statistics (triple j of channel c of group q at ((q C + c) P + j) 3), [G,C,P,2] for the backward.
  * saved_mean and saved_var are [G,C]: group q's mu and sigma^2.
- * Running statistics: one block per channel folds the triples of all G groups (thread q group q, the fold of the apply blocks) and one thread
+ * Running statistics: the first block of (channel, group q) writes saved_mean / saved_var [q, c] from its own fold; the first block of
+ *   (channel, group 0) also folds, where G > 1, the triples of the other groups (thread q group q, the fold of the apply blocks) and one thread
  *   then applies, in float32 with separate multiplications and additions, for q = 0 .. G - 1 ascending: running_mean = (1 - m) running_mean +
  *   m mu_q, running_var = (1 - m) running_var + m u_q (u_q the unbiased variance rounded once) -- exactly what G successive ungrouped calls on
  *   the slabs leave behind.  One thread of the launch adds G to *num_batches_tracked.

@@ -1,5 +1,5 @@
 """Times FeatureNet over the V views of one sample: the device loop (one call per view, as CascadeMVSNet's feature_views="loop" runs it), the device
-batched pass (FeatureNet.forward_views: one pass over [V,3,H,W], every batch-norm keeping its statistics per view through csrc/bn_groups.hip) and
+batched pass (FeatureNet.forward_views: one pass over [V,3,H,W], every batch-norm keeping its statistics per view through the group dimension of csrc/bn.hip) and
 torch's loop (torch's layers, one call per view), of the SAME module, in the same process, alternating.
 
     python scripts/time_feature_views.py [--reps 20] [--out profiles/feature_views.md]

@@ -1,4 +1,4 @@
-"""Shared cases of the FeatureNet-over-all-views tests (csrc/bn_groups.hip, ops.batch_norm_train(groups=), FeatureNet.forward_views,
+"""Shared cases of the FeatureNet-over-all-views tests (the group dimension of csrc/bn.hip, ops.batch_norm_train(groups=), FeatureNet.forward_views,
 CascadeMVSNet(feature_views="batched")) and the float64 restatement the batched pass is measured against.
 
 The restatement of the module is feature_train_cases.feature_net applied VIEW BY VIEW, as the reference runs its feature net: every view is a

@@ -45,10 +45,12 @@ def test_the_four_symbols_and_structs_are_registered_and_the_abi_stays_at_6(L):
         assert struct._fields_ == [("G", C.c_int64)] + base._fields_
         assert L.lib().ucnerf_sizeof((name + "_params").encode()) == C.sizeof(struct) == C.sizeof(base) + 8, name
     assert hdr.index("ucnerf_conv2d_bias_grad(") < hdr.index("struct ucnerf_bn_stats_groups_params {")       # appended: nothing above moved
-    assert "bn_groups.hip" in SOURCES and os.path.join(CSRC, "bn_device.h") in HEADERS
-    for unit in ("bn.hip", "bn_groups.hip"):                               # one code path: both units run the header's device functions
-        src = open(os.path.join(CSRC, unit)).read()
-        assert '#include "bn_device.h"' in src and "bn_slice_triple(" in src and "chan(const" not in src, unit
+    # one code path: a single batch-norm source with four kernels behind all eight entry points
+    assert [f for f in sorted(os.listdir(CSRC)) if f.startswith("bn")] == ["bn.hip"] and "bn.hip" in SOURCES
+    assert not any(os.path.basename(h).startswith("bn") for h in HEADERS)
+    assert open(os.path.join(CSRC, "bn.hip")).read().count("__global__") == 4
+    for name in sum(PAIRS, ()):
+        assert C.cast(getattr(raw, name), C.c_void_p).value, name
     from uc_nerf_amd import ops
     from uc_nerf_amd.ops import cnn
     assert ops.BN_MAX_GROUPS is cnn.BN_MAX_GROUPS == VC.MAX_GROUPS

@@ -354,3 +354,85 @@ def test_cascade_with_cnns_train_mode_end_to_end(cascade_net, pad):
     (variance, prob), = seen
     assert variance.shape == (1, 32, 48, H // 4, W // 4) and prob.shape == (1, 1, 48, H // 4, W // 4)
     held("stage-1 logits", prob, BC.cost_reg_net(variance, before, torch.float64)[1], BC.cost_reg_net(variance, before, torch.float32)[1])
+
+
+# ------------------------------------------------------------------------------------------------ 9. the ungrouped entry points are G = 1
+# Nothing in Python launches the four ungrouped entry points any more (ops.batch_norm_train fills the grouped structs for every G), so they are
+# called here through ctypes and held bit for bit to the `_groups` entry points at G = 1 on the same inputs.
+RAW_CASES = (((2, 3, 7), False),                                           # scalar quads with a ragged tail
+             ((1, 4, 4352), False),                                        # two partials on the vector path
+             ((3, 2, 4100), False),                                        # four partials on the vector path, an image boundary inside a slice
+             ((2, 3, 8), True))                                            # a vector-eligible S on a base one float past 16-byte alignment: the scalar walk
+
+
+def _guarded(rows, width):
+    """`rows` float64 rows of `width` inside a NaN-filled buffer, one guard row on either side -> (the buffer, the address of the first row)."""
+    buf = torch.full(((rows + 2) * width,), float("nan"), dtype=torch.float64, device=DEV)
+    return buf, buf.data_ptr() + 8 * width
+
+
+def _guards_held(buf, width):
+    return bool(torch.isnan(buf[:width]).all()) and bool(torch.isnan(buf[-width:]).all()) and not bool(torch.isnan(buf[width:-width]).any())
+
+
+def _placed(t, misaligned):
+    """t on the device; `misaligned`: at a base address one float past a 16-byte boundary."""
+    if not misaligned:
+        return t.to(DEV)
+    view = torch.empty(t.numel() + 4, device=DEV)[1:1 + t.numel()].view(t.shape)
+    assert view.data_ptr() % 16 == 4
+    return view.copy_(t)
+
+
+def _raw_entries(grouped, case, grad, relu, skip, misaligned):
+    """The four launches through the ungrouped or the grouped (G = 1) entry points, workspaces sized exactly -> every result by name."""
+    from uc_nerf_amd import _lib as L
+    from uc_nerf_amd.ops._core import _launch
+    n, Ch, S_ = case.shape
+    P = partials(n, S_)
+
+    def launch(kind):
+        p = getattr(L, kind + ("GroupsParams" if grouped else "Params"))()
+        if grouped:
+            p.G = 1
+        p.n, p.C, p.S = n, Ch, S_
+        return p, lambda symbol: _launch(symbol + ("_groups" if grouped else ""), p, DEV)
+
+    y, g, sk = _placed(case.y, misaligned), _placed(grad, misaligned), case.skip.to(DEV) if skip else None
+    gamma, beta = case.gamma.to(DEV), case.beta.to(DEV)
+    res = {"out": torch.empty(case.shape, device=DEV), "saved_mean": torch.empty(Ch, device=DEV), "saved_var": torch.empty(Ch, device=DEV),
+           "running_mean": case.rm.to(DEV), "running_var": case.rv.to(DEV), "num_batches_tracked": torch.tensor(7, dtype=torch.int64, device=DEV),
+           "grad_y": torch.empty(case.shape, device=DEV), "grad_weight": torch.empty(Ch, device=DEV), "grad_bias": torch.empty(Ch, device=DEV)}
+    triples, triples_at = _guarded(Ch * P, 3)
+    s, go = launch("BnStats")
+    s.workspace_triples, s.y, s.workspace = Ch * P, y.data_ptr(), triples_at
+    go("ucnerf_bn_stats")
+    a, go = launch("BnApply")
+    a.workspace_triples, a.eps, a.momentum, a.relu = Ch * P, BC.EPS, BC.MOMENTUM, int(relu)
+    a.y, a.workspace, a.weight, a.bias, a.skip = y.data_ptr(), triples_at, gamma.data_ptr(), beta.data_ptr(), 0 if sk is None else sk.data_ptr()
+    for name in ("out", "saved_mean", "saved_var", "running_mean", "running_var", "num_batches_tracked"):
+        setattr(a, name, res[name].data_ptr())
+    go("ucnerf_bn_apply")
+    pairs, pairs_at = _guarded(Ch * P, 2)
+    for kind, symbol in (("BnBwdReduce", "ucnerf_bn_bwd_reduce"), ("BnBwdApply", "ucnerf_bn_bwd_apply")):
+        q, go = launch(kind)
+        q.workspace_pairs, q.eps, q.relu, q.g, q.y, q.workspace = Ch * P, BC.EPS, int(relu), g.data_ptr(), y.data_ptr(), pairs_at
+        q.saved_mean, q.saved_var, q.weight, q.bias = res["saved_mean"].data_ptr(), res["saved_var"].data_ptr(), gamma.data_ptr(), beta.data_ptr()
+        if kind == "BnBwdApply":
+            q.grad_y, q.grad_weight, q.grad_bias = res["grad_y"].data_ptr(), res["grad_weight"].data_ptr(), res["grad_bias"].data_ptr()
+        go(symbol)
+    torch.cuda.synchronize()
+    assert _guards_held(triples, 3) and _guards_held(pairs, 2), "a workspace of exactly C P rows was overrun or not filled"
+    return res
+
+
+@pytest.mark.parametrize("shape,misaligned", RAW_CASES, ids=str)
+def test_ungrouped_entry_points_are_the_grouped_ones_at_one_group(shape, misaligned):
+    assert partials(2, 7) == 1 and partials(1, 4352) == 2 and partials(3, 4100) == 4 and partials(2, 8) == 1
+    case = Case(shape, 421)
+    grad = torch.randn(shape, generator=torch.Generator().manual_seed(422))
+    for relu, skip in itertools.product((True, False), (False, True)):
+        plain, grouped = (_raw_entries(way, case, grad, relu, skip, misaligned) for way in (False, True))
+        for name, t in plain.items():
+            assert torch.equal(t, grouped[name]) and not bool(torch.isnan(t).any()), (name, relu, skip)
+        assert int(plain["num_batches_tracked"]) == 8

@@ -1,4 +1,4 @@
-"""FeatureNet over all views in one pass on the GPU (csrc/bn_groups.hip, ops.batch_norm_train(groups=), FeatureNet.forward_views,
+"""FeatureNet over all views in one pass on the GPU (the group dimension of csrc/bn.hip, ops.batch_norm_train(groups=), FeatureNet.forward_views,
 CascadeMVSNet(feature_views="batched")): the grouped batch-norm against G ungrouped calls on the G slabs -- bit for bit in everything but the
 parameter gradients, which are float64 sums over the groups rounded once and are held to that --, its workspace, guards and determinism, the
 module's batched pass against the per-view loop on a deep copy, a second training step, one training step of the whole cascade and the launch
@@ -68,7 +68,7 @@ def stream():
 
 
 def raw_forward(G, y, gamma, beta, bufs, relu, skip, out, ws, saved):
-    """The two grouped entry points through the C ABI (also for G == 1, which the ops send to the ungrouped ones)."""
+    """The two grouped entry points through the C ABI (also for G == 1; the ungrouped entry points against these at G == 1: tests/test_hip_bn.py)."""
     Lb = lib()
     n, C, S_, P = geometry(y, G)
     s, a = Lb.BnStatsGroupsParams(), Lb.BnApplyGroupsParams()
@@ -203,6 +203,28 @@ def test_grouped_parameter_gradients_are_exact_on_an_integer_lattice(shape, relu
     for name, a, per_slab in (("grad_weight", got[1], want[1]), ("grad_bias", got[2], want[2])):
         assert bool((per_slab * 2 == (per_slab * 2).round()).all()) and float(per_slab.abs().max()) > 0, name
         assert torch.equal(a, per_slab.sum(0)) and torch.equal(a.double(), per_slab.double().sum(0)), (name, shape)
+
+
+@pytest.mark.parametrize("relu", (False, True))
+def test_grouped_parameter_gradients_are_summed_in_float64_and_rounded_once(relu):
+    """Groups 0 and 1 hold the same y and opposite gradients a thousand times the size of group 2's: their terms cancel EXACTLY in a float64 sum
+    (B_1 = -B_0 and A_1 = -A_0 bit for bit, the same r), so grad_weight and grad_bias are the ungrouped backward's bits on slab 2 alone.  A sum
+    kept in float32 rounds the first term before the second arrives and leaves that rounding, large against group 2's term, in the result."""
+    n, C, S_ = 2, 5, 37
+    g = torch.Generator().manual_seed(66)
+    y0, go0 = 1.5 * torch.randn(n, C, S_, generator=g) + 0.5, 1000.0 * torch.randn(n, C, S_, generator=g)
+    y = torch.cat([y0, y0, torch.randn(n, C, S_, generator=g)]).to(DEV)
+    go = torch.cat([go0, -go0, 1e-3 * torch.randn(n, C, S_, generator=g)]).to(DEV)
+    gamma, beta = (0.6 + 0.8 * torch.rand(C, generator=g)).to(DEV), (0.3 * torch.randn(C, generator=g)).to(DEV)
+    _, mean, var = grouped_forward(3, y, gamma, beta, [t.to(DEV) for t in VC.buffers(C, 67)], relu, None, False)
+    saved = (mean.contiguous(), var.contiguous())
+    assert torch.equal(saved[0][0], saved[0][1]) and torch.equal(saved[1][0], saved[1][1])
+    got = grouped_backward(3, go, y, saved, gamma, beta, relu, False)
+    want = slab_backward(3, go, y, saved, gamma, beta, relu)
+    assert torch.equal(got[0], want[0])
+    for name, a, per_slab in (("grad_weight", got[1], want[1]), ("grad_bias", got[2], want[2])):
+        assert torch.equal(per_slab[0], -per_slab[1]) and float(per_slab[0].abs().min()) > 100 * float(per_slab[2].abs().max()) > 0, name
+        assert torch.equal(a, per_slab[2]), (name, relu)
 
 
 # ------------------------------------------------------------------------------------------------ 3. workspace, guards, determinism
@@ -430,7 +452,8 @@ def test_batched_forward_issues_one_view_s_launches_for_three_views(monkeypatch)
             net(imgs[:, i])
         loop = list(counted)
     assert len(one_view) == 13 + 2 * 8 == len(batched) and len(loop) == 3 * len(one_view)
-    assert [n.replace("_groups", "") for n in batched] == one_view and sum(n.endswith("_groups") for n in batched) == 16
+    # (one view is G = 1 of the same entry points: the very same sequence of symbols)
+    assert batched == one_view and sum(n.endswith("_groups") for n in batched) == 16 and not any("ucnerf_bn" in n and not n.endswith("_groups") for n in batched)
 
 
 def test_zz_largest_share_of_the_bars():

@@ -57,7 +57,7 @@ class Conv3d(nn.Module):
         if stride not in (1, 2):
             raise AssertionError("stride 1 or 2")
         self.out_channels, self.kernel_size, self.stride = out_channels, kernel_size, stride
-        self.conv = nn.Conv3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
+        self.conv = (nn.ConvTranspose3d if self.transposed else nn.Conv3d)(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
         self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
         self.relu = relu
 
@@ -68,24 +68,9 @@ class Conv3d(nn.Module):
         return F.relu(x) if self.relu else x
 
 
-class Deconv3d(nn.Module):
-    """mvs_models.py:154-195: transposed conv (bias only without bn) -> BatchNorm3d -> ReLU."""
+class Deconv3d(Conv3d):
+    """mvs_models.py:154-195: transposed conv (bias only without bn) -> BatchNorm3d -> ReLU: Conv3d's body around an nn.ConvTranspose3d."""
     transposed = True
-
-    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, relu=True, bn=True, bn_momentum=0.1, **kwargs):
-        super().__init__()
-        if stride not in (1, 2):
-            raise AssertionError("stride 1 or 2")
-        self.out_channels, self.kernel_size, self.stride = out_channels, kernel_size, stride
-        self.conv = nn.ConvTranspose3d(in_channels, out_channels, kernel_size, stride=stride, bias=(not bn), **kwargs)
-        self.bn = nn.BatchNorm3d(out_channels, momentum=bn_momentum) if bn else None
-        self.relu = relu
-
-    def forward(self, x):
-        x = self.conv(x)
-        if self.bn is not None:
-            x = self.bn(x)
-        return F.relu(x) if self.relu else x
 
 
 def fold_conv_bn(layer, dtype=torch.float64):
@@ -152,21 +137,22 @@ def _device_route(module, x):
     return module.inference == "device" and not module.training and not torch.is_grad_enabled() and x.is_cuda
 
 
-def _batch_stats_route(module, x):
-    """train() + no_grad on the device with batch_stats="device", every batch-norm keeping running statistics with a float momentum."""
-    if not (module.inference == "device" and module.batch_stats == "device" and module.training and not torch.is_grad_enabled() and x.is_cuda):
-        return False
+def _batch_norms_on_device(module):
+    """Every batch-norm keeps running statistics with a float momentum: what the batch-norm kernels update."""
     return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
                for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
+
+
+def _batch_stats_route(module, x):
+    """train() + no_grad on the device with batch_stats="device", every batch-norm one the kernels update."""
+    return (module.inference == "device" and module.batch_stats == "device" and module.training and not torch.is_grad_enabled() and x.is_cuda
+            and _batch_norms_on_device(module))
 
 
 def _training_route(module, x):
-    """train() + grad enabled on the device with training="device", every batch-norm keeping running statistics with a float momentum."""
-    if not (getattr(module, "training_route", "torch") == "device" and module.inference == "device" and module.training and torch.is_grad_enabled()
-            and x.is_cuda):
-        return False
-    return all(bn.track_running_stats and bn.running_mean is not None and isinstance(bn.momentum, float)
-               for bn in module.modules() if isinstance(bn, nn.modules.batchnorm._BatchNorm))
+    """train() + grad enabled on the device with training="device", every batch-norm one the kernels update."""
+    return (getattr(module, "training_route", "torch") == "device" and module.inference == "device" and module.training and torch.is_grad_enabled()
+            and x.is_cuda and _batch_norms_on_device(module))
 
 
 def _conv_weights(module):
@@ -243,22 +229,31 @@ class FeatureNet(nn.Module):
             out.append(ops.conv2d_dgrad_pack(conv.weight.detach().float(), conv.stride[0], conv.padding[0]))
         return out
 
-    def forward(self, x):
-        if _device_route(self, x):
-            return self._forward_device(x)
-        if _batch_stats_route(self, x):
-            return self._forward_device(x, batch_stats=True)
-        if _training_route(self, x):
-            return self._forward_train(x)
-        conv0 = self.conv0(x)
-        conv1 = self.conv1(conv0)
-        conv2 = self.conv2(conv1)
-        outputs = {"stage1": self.out1(conv2)}
-        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + self.inner1(conv1)
-        outputs["stage2"] = self.out2(intra)
-        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + self.inner2(conv0)
-        outputs["stage3"] = self.out3(intra)
+    @staticmethod
+    def _pyramid(x, run, trunk=None):
+        """The topology, once for every route: `run(i, t)` is layer i of `_layers()` on t.  `trunk(k, t)`: conv0 / conv1 / conv2 (k = 0, 1, 2) as a
+        whole -- torch's route calls the nn.Sequential containers themselves, so that hooks on them fire; without it, their layers one by one."""
+        if trunk is None:
+            def trunk(k, t):
+                for i in ((0, 1), (2, 3, 4), (5, 6, 7))[k]:
+                    t = run(i, t)
+                return t
+        conv0 = trunk(0, x)
+        conv1 = trunk(1, conv0)
+        conv2 = trunk(2, conv1)
+        outputs = {"stage1": run(8, conv2)}
+        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + run(9, conv1)
+        outputs["stage2"] = run(11, intra)
+        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0)
+        outputs["stage3"] = run(12, intra)
         return outputs
+
+    def forward(self, x):
+        run = self._device_runner(x)
+        if run is not None:
+            return self._pyramid(x, run)
+        layers = self._layers()
+        return self._pyramid(x, lambda i, t: layers[i](t), lambda k, t: (self.conv0, self.conv1, self.conv2)[k](t))
 
     def forward_views(self, imgs):
         """The features of all V views of one sample in ONE pass: imgs [1,V,3,H,W] or [V,3,H,W] -> {"stage1": [V,4c,H/4,W/4], "stage2":
@@ -274,68 +269,44 @@ class FeatureNet(nn.Module):
                                % (tuple(imgs.shape) if torch.is_tensor(imgs) else type(imgs),))
         x = imgs[0] if imgs.dim() == 5 else imgs
         V = x.shape[0]
-        if _device_route(self, x):
-            return self._forward_device(x)
-        if V <= ops.BN_MAX_GROUPS:
-            if _batch_stats_route(self, x):
-                return self._forward_device(x, batch_stats=True, groups=V)
-            if _training_route(self, x):
-                return self._forward_train(x, groups=V)
+        run = self._device_runner(x, groups=V)
+        if run is not None:
+            return self._pyramid(x, run)
         per_view = [self.forward(x[i:i + 1]) for i in range(V)]
         return {key: torch.cat([out[key] for out in per_view]) for key in per_view[0]}
 
-    def _forward_device(self, x, batch_stats=False, groups=1):
+    def _device_runner(self, x, groups=1):
+        """`_pyramid`'s per-layer runner for the device route `forward`'s predicates choose for x -- folded, batch statistics or training, the
+        batch-norms of the last two keeping their statistics per group of images -- or None where torch's layers run (also where `groups` is
+        more than the kernels take)."""
+        folded, stats = _device_route(self, x), False
+        if not folded:
+            stats = _batch_stats_route(self, x)
+            if not (stats or _training_route(self, x)) or groups > ops.BN_MAX_GROUPS:
+                return None
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
             raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
                                "it), got %s" % (tuple(x.shape),))
-        folded = self._raw_cache.get(self, self._raw) if batch_stats else self._cache.get(self, self._fold)
-        layers = self._layers()
-
-        def run(i, t, relu):
-            conv = layers[i].conv if hasattr(layers[i], "conv") else layers[i]
-            if not batch_stats:
-                return ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=relu)
-            if conv is layers[i]:                            # no batch-norm: the convolution with its own bias, as above
-                bias = conv.bias.detach() if conv.bias is not None else folded[i][1]
-                return ops.conv2d_bias_relu(t, folded[i][0], bias, stride=conv.stride[0], pad=conv.padding[0], relu=relu)
-            y = ops.conv2d_bias_relu(t, folded[i][0], folded[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=False)
-            return _bn_train(layers[i], y, groups=groups)
-
-        conv0 = run(1, run(0, x, True), True)
-        conv1 = run(4, run(3, run(2, conv0, True), True), True)
-        conv2 = run(7, run(6, run(5, conv1, True), True), True)
-        outputs = {"stage1": run(8, conv2, False)}
-        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + run(9, conv1, False)
-        outputs["stage2"] = run(11, intra, False)
-        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0, False)
-        outputs["stage3"] = run(12, intra, False)
-        return outputs
-
-    def _forward_train(self, x, groups=1):
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 4 or x.shape[3] % 4:
-            raise RuntimeError("uc_nerf_amd FeatureNet: the device route takes [n,3,H,W] with H and W divisible by 4 (the pyramid's additions need "
-                               "it), got %s" % (tuple(x.shape),))
-        f, d = self._raw_cache.get(self, self._raw), self._dgrad_cache.get(self, self._dgrad)
+        f = self._cache.get(self, self._fold) if folded else self._raw_cache.get(self, self._raw)
+        d = None if folded or stats else self._dgrad_cache.get(self, self._dgrad)
         layers = self._layers()
 
         def run(i, t):
             layer = layers[i]
-            if hasattr(layer, "conv"):
-                conv, bn = layer.conv, layer.bn
+            conv, bn = (layer.conv, layer.bn) if hasattr(layer, "conv") else (layer, None)
+            if d is not None:                                # training: forward and backward on the kernels
+                if bn is None:
+                    return ops.conv2d_train(t, conv.weight, conv.bias, stride=conv.stride[0], pad=conv.padding[0], packed=f[i][0], packed_dgrad=d[i])
                 return ops.conv2d_bn_train(t, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                            momentum=bn.momentum, eps=bn.eps, stride=conv.stride[0], pad=conv.padding[0], relu=layer.relu,
                                            packed=f[i][0], packed_dgrad=d[i], groups=groups)
-            return ops.conv2d_train(t, layer.weight, layer.bias, stride=layer.stride[0], pad=layer.padding[0], packed=f[i][0], packed_dgrad=d[i])
+            if folded or bn is None:                         # (batch statistics, no batch-norm: the convolution with its own bias)
+                bias = f[i][1] if folded or conv.bias is None else conv.bias.detach()
+                return ops.conv2d_bias_relu(t, f[i][0], bias, stride=conv.stride[0], pad=conv.padding[0], relu=getattr(layer, "relu", False))
+            y = ops.conv2d_bias_relu(t, f[i][0], f[i][1], stride=conv.stride[0], pad=conv.padding[0], relu=False)
+            return _bn_train(layer, y, groups=groups)
 
-        conv0 = run(1, run(0, x))
-        conv1 = run(4, run(3, run(2, conv0)))
-        conv2 = run(7, run(6, run(5, conv1)))
-        outputs = {"stage1": run(8, conv2)}
-        intra = F.interpolate(conv2, scale_factor=2, mode="nearest") + run(9, conv1)
-        outputs["stage2"] = run(11, intra)
-        intra = F.interpolate(intra, scale_factor=2, mode="nearest") + run(10, conv0)
-        outputs["stage3"] = run(12, intra)
-        return outputs
+        return run
 
 
 class CostRegNet(nn.Module):
@@ -395,35 +366,9 @@ class CostRegNet(nn.Module):
                          torch.zeros(cout, device=conv.weight.device))
         return out
 
-    def forward(self, x):
-        if _device_route(self, x):
-            return self._forward_device(x)
-        if _batch_stats_route(self, x):
-            return self._forward_device(x, batch_stats=True)
-        if _training_route(self, x):
-            return self._forward_train(x)
-        conv0 = self.conv0(x)
-        conv2 = self.conv2(self.conv1(conv0))
-        conv4 = self.conv4(self.conv3(conv2))
-        x = self.conv6(self.conv5(conv4))
-        x = conv4 + self.conv7(x)
-        x = conv2 + self.conv9(x)
-        cost = conv0 + self.conv11(x)
-        return cost, self.prob(cost)
-
-    def _forward_device(self, x, batch_stats=False):
-        if x.dim() != 5 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
-            raise RuntimeError("uc_nerf_amd CostRegNet: the device route takes [n,C,D,H,W] with D, H and W divisible by 8 (three halvings, three "
-                               "doublings and the skip additions between them), got %s" % (tuple(x.shape),))
-        f = self._raw_cache.get(self, self._raw) if batch_stats else self._cache.get(self, self._fold)
-
-        def conv(name, t, stride=1, skip=None, relu=True):
-            layer = getattr(self, name)
-            if not batch_stats or getattr(layer, "bn", None) is None:
-                return ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=relu, skip=skip, transposed=f[name][0].transposed)
-            y = ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=False, skip=None, transposed=f[name][0].transposed)
-            return _bn_train(layer, y, skip)
-
+    @staticmethod
+    def _hourglass(x, conv):
+        """The topology, once for every route: `conv(name, t, stride, skip)` is the named layer on t with `skip` added to its result."""
         conv0 = conv("conv0", x)
         conv2 = conv("conv2", conv("conv1", conv0, 2))
         conv4 = conv("conv4", conv("conv3", conv2, 2))
@@ -431,30 +376,45 @@ class CostRegNet(nn.Module):
         x = conv("conv7", x, 2, skip=conv4)
         x = conv("conv9", x, 2, skip=conv2)
         cost = conv("conv11", x, 2, skip=conv0)
-        return cost, conv("prob", cost, relu=False)
+        return cost, conv("prob", cost)
 
+    def forward(self, x):
+        return self._hourglass(x, self._device_conv(x) or self._torch_conv)
 
-    def _forward_train(self, x):
+    def _torch_conv(self, name, t, stride=1, skip=None):
+        """torch's layer (the stride is its own); the skip is added OUTSIDE the layer, as the reference adds it."""
+        y = getattr(self, name)(t)
+        return y if skip is None else skip + y
+
+    def _device_conv(self, x):
+        """`_hourglass`'s layer function for the device route `forward`'s predicates choose for x -- folded, batch statistics or training, the
+        skip additions inside the launches -- or None where torch's layers run."""
+        folded, stats = _device_route(self, x), False
+        if not folded:
+            stats = _batch_stats_route(self, x)
+            if not (stats or _training_route(self, x)):
+                return None
         if x.dim() != 5 or x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
             raise RuntimeError("uc_nerf_amd CostRegNet: the device route takes [n,C,D,H,W] with D, H and W divisible by 8 (three halvings, three "
                                "doublings and the skip additions between them), got %s" % (tuple(x.shape),))
-        f, d = self._raw_cache.get(self, self._raw), self._dgrad_cache.get(self, self._dgrad)
+        f = self._cache.get(self, self._fold) if folded else self._raw_cache.get(self, self._raw)
+        d = None if folded or stats else self._dgrad_cache.get(self, self._dgrad)
 
         def conv(name, t, stride=1, skip=None):
             layer = getattr(self, name)
-            bn = layer.bn
-            return ops.conv3d_bn_train(t, layer.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                       momentum=bn.momentum, eps=bn.eps, stride=stride, pad=1, relu=layer.relu, skip=skip,
-                                       transposed=layer.transposed, packed=f[name][0], packed_dgrad=d[name])
+            bn = getattr(layer, "bn", None)
+            if d is not None:                                # training: forward and backward on the kernels
+                if bn is None:
+                    return ops.conv3d_train(t, layer.weight, 1, 1, packed=f[name][0], packed_dgrad=d[name])
+                return ops.conv3d_bn_train(t, layer.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                           momentum=bn.momentum, eps=bn.eps, stride=stride, pad=1, relu=layer.relu, skip=skip,
+                                           transposed=layer.transposed, packed=f[name][0], packed_dgrad=d[name])
+            if folded or bn is None:
+                return ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=getattr(layer, "relu", False), skip=skip, transposed=f[name][0].transposed)
+            y = ops.conv3d(t, f[name][0], f[name][1], stride=stride, pad=1, relu=False, skip=None, transposed=f[name][0].transposed)
+            return _bn_train(layer, y, skip)
 
-        conv0 = conv("conv0", x)
-        conv2 = conv("conv2", conv("conv1", conv0, 2))
-        conv4 = conv("conv4", conv("conv3", conv2, 2))
-        x = conv("conv6", conv("conv5", conv4, 2))
-        x = conv("conv7", x, 2, skip=conv4)
-        x = conv("conv9", x, 2, skip=conv2)
-        cost = conv("conv11", x, 2, skip=conv0)
-        return cost, ops.conv3d_train(cost, self.prob.weight, 1, 1, packed=f["prob"][0], packed_dgrad=d["prob"])
+        return conv
 
 
 def mvs_depth_regression(p, depth_values):                 # mvs_models.py:574-579

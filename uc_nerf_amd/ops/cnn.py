@@ -2,7 +2,8 @@
 their backward: the weight gradient (csrc/conv3d_bwd.hip), the input gradient on the forward kernel, the batch-norm backward with the ReLU mask,
 and the differentiable layer CostRegNet's training route is made of.  The same for FeatureNet's 2-D layers: the weight, stride-2 input and bias
 gradients of csrc/conv2d_bwd.hip and the two differentiable layer functions of its training route.  `groups=` on the batch-norm functions keeps
-the statistics per group of images (csrc/bn_groups.hip): FeatureNet over all the views of a sample in one pass."""
+the statistics per group of images (the same kernels and entry points: `groups=1` is their G = 1): FeatureNet over all the views of a sample in one
+pass."""
 import torch
 
 from .. import _lib as L
@@ -75,7 +76,7 @@ def conv3d(x, weight, bias, stride=1, pad=0, relu=True, skip=None, transposed=Fa
     return y
 
 
-BN_MAX_GROUPS = 64                                         # csrc/bn_device.h: BN_MAX_GROUPS
+BN_MAX_GROUPS = 64                                         # csrc/bn.hip: BN_MAX_GROUPS
 
 
 def _bn_groups(groups, y, who):
@@ -87,15 +88,27 @@ def _bn_groups(groups, y, who):
     return groups
 
 
+def _bn_args(who, y, shape, *named):
+    """Arguments of the batch-norm functions, (tensor, name) each: contiguous float32 tensors on y's device, of `shape` or (None) of y's own
+    -> them, detached, in the order given (one call for several: the small layers are bound by the host's time per launch)."""
+    want, dev, out = y.shape if shape is None else shape, y.device, []
+    for t, name in named:
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and t.shape == want and t.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.%s: %s must be a contiguous float32 %s" % (who, name, "tensor of y's shape %s on its device" % (tuple(y.shape),)
+                                                                                     if shape is None else "%s tensor on y's device" % (list(shape),)))
+        out.append(t.detach())
+    return out
+
+
 def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tracked, momentum=0.1, eps=1e-5, relu=True, skip=None, out=None,
                      return_stats=False, groups=1):
     """Train-mode batch-norm of y [n,C,*spatial] (float32, contiguous, on the device) with the statistics of the batch itself, forward only
-    (csrc/bn.hip: `ucnerf_bn_stats` then `ucnerf_bn_apply`, the order of every sum fixed, nothing read back): out = act((y - mean) / sqrt(var +
+    (csrc/bn.hip: `ucnerf_bn_stats_groups` then `ucnerf_bn_apply_groups`, the order of every sum fixed, nothing read back): out = act((y - mean) / sqrt(var +
     eps) * weight + bias) (+ skip), var the biased variance, act ReLU with `relu`, `skip` added AFTER the activation.  `running_mean`,
     `running_var` (float32 [C]) and `num_batches_tracked` (one int64) move in place as nn.BatchNorm moves them (the unbiased variance, momentum a
     float in (0, 1]); their version counters are bumped, since the kernels write through raw pointers.  `out`: a tensor like y to write into, y
     itself for in place.  -> out, or (out, saved_mean, saved_var) with `return_stats`.  No autograd: inputs that require grad are used detached.
-    `groups` = G > 1 (csrc/bn_groups.hip, the same two launches): the first dimension is G groups of n / G consecutive images, each normalised
+    `groups` = G > 1 (the same two launches; `groups=1` is their G = 1): the first dimension is G groups of n / G consecutive images, each normalised
     with its OWN statistics, bit for bit what G calls on the G slabs give, the running statistics moved G times in ascending group order;
     saved_mean and saved_var then are [G,C]."""
     if torch.is_tensor(y) and y.dim() >= 2 and 0 < y.numel() == y.shape[1]:     # n S == 1: torch's own refusal, before anything else is looked at
@@ -111,38 +124,27 @@ def batch_norm_train(y, weight, bias, running_mean, running_var, num_batches_tra
     S = y.numel() // (G * n * C)
     if momentum is None or not 0.0 < float(momentum) <= 1.0 or not float(eps) > 0.0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train: momentum=%r eps=%r (a float momentum in (0, 1], a positive eps)" % (momentum, eps))
-    per_channel = []
-    for t, name in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == (C,) and t.is_contiguous()):
-            raise RuntimeError("uc_nerf_amd.batch_norm_train: %s must be a contiguous float32 [%d] tensor on y's device" % (name, C))
-        per_channel.append(t.detach())
-    weight, bias = per_channel[0], per_channel[1]
+    weight, bias, _, _ = _bn_args("batch_norm_train", y, (C,), (weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var"))
     nbt = num_batches_tracked
     if not (torch.is_tensor(nbt) and nbt.dtype == torch.int64 and nbt.numel() == 1 and nbt.device == y.device):
         raise RuntimeError("uc_nerf_amd.batch_norm_train: num_batches_tracked must be one int64 element on y's device")
-    for t, name in ((skip, "skip"), (out, "out")):
-        if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == y.device and t.shape == y.shape and t.is_contiguous()):
-            raise RuntimeError("uc_nerf_amd.batch_norm_train: %s must be a contiguous float32 tensor of y's shape %s on its device" % (name, tuple(y.shape)))
     if skip is not None:
-        skip = skip.detach()
-    out = torch.empty_like(y) if out is None else out.detach()
+        skip, = _bn_args("batch_norm_train", y, None, (skip, "skip"))
+    out = torch.empty_like(y) if out is None else _bn_args("batch_norm_train", y, None, (out, "out"))[0]
     P = L.lib().ucnerf_bn_partials(n, S)
     if P < 0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
                            % (tuple(y.shape),))
-    workspace = torch.empty((G, C, P, 3) if G > 1 else (C, P, 3), dtype=torch.float64, device=y.device)
+    workspace = torch.empty((G, C, P, 3), dtype=torch.float64, device=y.device)
     saved = torch.empty((2, G, C) if G > 1 else (2, C), device=y.device)
-    s = L.BnStatsGroupsParams() if G > 1 else L.BnStatsParams()
-    a = L.BnApplyGroupsParams() if G > 1 else L.BnApplyParams()
-    if G > 1:
-        s.G = a.G = G
-    s.n, s.C, s.S, s.workspace_triples, s.y, s.workspace = n, C, S, G * C * P, _ptr(y), _ptr(workspace)
-    _launch("ucnerf_bn_stats_groups" if G > 1 else "ucnerf_bn_stats", s, y.device)
-    a.n, a.C, a.S, a.workspace_triples, a.eps, a.momentum, a.relu = n, C, S, G * C * P, float(eps), float(momentum), int(bool(relu))
+    s, a = L.BnStatsGroupsParams(), L.BnApplyGroupsParams()
+    s.G, s.n, s.C, s.S, s.workspace_triples, s.y, s.workspace = G, n, C, S, G * C * P, _ptr(y), _ptr(workspace)
+    _launch("ucnerf_bn_stats_groups", s, y.device)
+    a.G, a.n, a.C, a.S, a.workspace_triples, a.eps, a.momentum, a.relu = G, n, C, S, G * C * P, float(eps), float(momentum), int(bool(relu))
     a.y, a.workspace, a.weight, a.bias, a.skip, a.out = _ptr(y), _ptr(workspace), _ptr(weight), _ptr(bias), _ptr(skip), _ptr(out)
     a.saved_mean, a.saved_var, a.running_mean, a.running_var = _ptr(saved[0]), _ptr(saved[1]), _ptr(running_mean), _ptr(running_var)
     a.num_batches_tracked = _ptr(nbt)
-    _launch("ucnerf_bn_apply_groups" if G > 1 else "ucnerf_bn_apply", a, y.device)
+    _launch("ucnerf_bn_apply_groups", a, y.device)
     for t in (running_mean, running_var, nbt):
         torch.autograd.graph.increment_version(t)
     if given is not None:
@@ -232,11 +234,11 @@ def conv3d_dgrad(grad_y, weight, x_shape, stride=1, pad=1, transposed=False):
 
 
 def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1e-5, relu=True, out=None, groups=1):
-    """The backward of `batch_norm_train` (csrc/bn.hip: `ucnerf_bn_bwd_reduce` then `ucnerf_bn_bwd_apply`, float64 sums in a fixed order, nothing
+    """The backward of `batch_norm_train` (csrc/bn.hip: `ucnerf_bn_bwd_reduce_groups` then `ucnerf_bn_bwd_apply_groups`, float64 sums in a fixed order, nothing
     read back): grad_out the gradient of act(bn(y)), y the tensor the forward normalised, saved_mean / saved_var what it returned with
     `return_stats`; the ReLU's mask is recomputed from y bit for bit.  `out`: a tensor like y for grad_y, grad_out itself for in place.
     -> (grad_y, grad_weight, grad_bias).  The skip's gradient is grad_out itself.
-    `groups` = G > 1 (csrc/bn_groups.hip), as in the forward: saved_mean / saved_var are its [G,C]; grad_y is, group by group, the ungrouped
+    `groups` = G > 1, as in the forward: saved_mean / saved_var are its [G,C]; grad_y is, group by group, the ungrouped
     backward's bit for bit; grad_weight and grad_bias [C] are the sums over the groups, added in float64 and rounded once."""
     G = _bn_groups(groups, y, "batch_norm_train_bwd")
     for t, name in ((grad_out, "grad_out"), (y, "y")):
@@ -249,32 +251,25 @@ def batch_norm_train_bwd(grad_out, y, saved_mean, saved_var, weight, bias, eps=1
     S = y.numel() // (G * n * C)
     if not float(eps) > 0.0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: eps=%r (a positive float)" % (eps,))
-    per_channel = []
-    for t, name in ((saved_mean, "saved_mean"), (saved_var, "saved_var"), (weight, "weight"), (bias, "bias")):
-        want = (G, C) if G > 1 and name.startswith("saved_") else (C,)
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == y.device and tuple(t.shape) == want and t.is_contiguous()):
-            raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: %s must be a contiguous float32 %s tensor on y's device" % (name, list(want)))
-        per_channel.append(t.detach())
-    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.float32 and out.device == y.device and out.shape == y.shape and out.is_contiguous()):
-        raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: out must be a contiguous float32 tensor of y's shape %s on its device" % (tuple(y.shape),))
+    per_channel = (_bn_args("batch_norm_train_bwd", y, (G, C) if G > 1 else (C,), (saved_mean, "saved_mean"), (saved_var, "saved_var"))
+                   + _bn_args("batch_norm_train_bwd", y, (C,), (weight, "weight"), (bias, "bias")))
+    if out is not None:
+        _bn_args("batch_norm_train_bwd", y, None, (out, "out"))
     P = L.lib().ucnerf_bn_partials(n, S)
     if P < 0:
         raise RuntimeError("uc_nerf_amd.batch_norm_train_bwd: y %s is outside what the kernels take (at least 2 and below 2^31 - 2^20 values per channel)"
                            % (tuple(y.shape),))
     grad_y = torch.empty_like(y) if out is None else out.detach()
-    workspace = torch.empty((G, C, P, 2) if G > 1 else (C, P, 2), dtype=torch.float64, device=y.device)
+    workspace = torch.empty((G, C, P, 2), dtype=torch.float64, device=y.device)
     grads = torch.empty((2, C), device=y.device)
-    r = L.BnBwdReduceGroupsParams() if G > 1 else L.BnBwdReduceParams()
-    a = L.BnBwdApplyGroupsParams() if G > 1 else L.BnBwdApplyParams()
+    r, a = L.BnBwdReduceGroupsParams(), L.BnBwdApplyGroupsParams()
     for q in (r, a):
-        if G > 1:
-            q.G = G
-        q.n, q.C, q.S, q.workspace_pairs, q.eps, q.relu = n, C, S, G * C * P, float(eps), int(bool(relu))
+        q.G, q.n, q.C, q.S, q.workspace_pairs, q.eps, q.relu = G, n, C, S, G * C * P, float(eps), int(bool(relu))
         q.g, q.y, q.workspace = _ptr(grad_out), _ptr(y), _ptr(workspace)
         q.saved_mean, q.saved_var, q.weight, q.bias = (_ptr(t) for t in per_channel)
     a.grad_y, a.grad_weight, a.grad_bias = _ptr(grad_y), _ptr(grads[0]), _ptr(grads[1])
-    _launch("ucnerf_bn_bwd_reduce_groups" if G > 1 else "ucnerf_bn_bwd_reduce", r, y.device)
-    _launch("ucnerf_bn_bwd_apply_groups" if G > 1 else "ucnerf_bn_bwd_apply", a, y.device)
+    _launch("ucnerf_bn_bwd_reduce_groups", r, y.device)
+    _launch("ucnerf_bn_bwd_apply_groups", a, y.device)
     return (grad_y if out is None else out), grads[0], grads[1]
 
 
