@@ -4,7 +4,8 @@
 
 Per case: 1..300 rays, 2..700 bin edges, 1..300 draws, weight rows drawn from eight families (uniform, cubed, one spike, sparse with exact zeros,
 all zero, tiny, huge dynamic range, a few negative), draws from five (uniform, sorted linspace shared by all rays, exact cdf entries, 0 and
-1 - 2^-24 at the ends, duplicated), optionally merged with a second sorted list that shares values with the samples (ties), optionally in the
+1 - 2^-24 at the ends, duplicated); run(families=..., draw_families=...) also reaches the non-finite members -- weight families 8 (one NaN in
+every other ray) and 9 (one +inf), draw family 5 (one NaN draw in every other ray) --, optionally merged with a second sorted list that shares values with the samples (ties), optionally in the
 `from_coarse` form the fused compositing launch uses (mid-point bins of z, w[1:-1]).
 
 Checked, all bit for bit (data/ray_utils.py:98-141,216-219):
@@ -12,8 +13,10 @@ Checked, all bit for bit (data/ray_utils.py:98-141,216-219):
   oracle.sample_pdf           ==  the same lines run by torch on the CPU of this box, whenever the row sums take ATen's vectorised path
                                   identically (they do on every AVX2/AVX-512 build: the fixtures pin lanes = 8) -- reported, not required
   with negative weights (a cdf that is not monotone; cannot occur in the reference) inds / samples  ==  torch-CPU's searchsorted, whose
-                                  binary search the device repeats step for step (the oracle counts entries <= u instead: equal only when monotone)
-  z_sorted                    ==  torch.sort(cat(samples, z_merge))
+                                  binary search the device repeats step for step, NaN included: it steps on !(cdf[mid] > u) as ATen's upper
+                                  bound does (the oracle counts entries <= u instead: equal only when monotone and free of NaN)
+  with the non-finite families    cdf, inds, samples  ==  the same lines run by torch on the CPU, NaN on the same elements
+  z_sorted                    ==  torch.sort(cat(samples, z_merge)), NaN last
   merge_rank                  is a permutation that places cat(samples, z_merge) into z_sorted
 Test infrastructure (imports oracle/): lives under tests/; tests/test_hip_round5.py runs a fixed set of its cases.
 """
@@ -50,6 +53,10 @@ def weights_of(rng, g, n, L, family):
         w[:, int(rng.randint(0, L))] = 3e5 * (1 + torch.rand(n, generator=g))
     elif family == 7:
         w[::2, int(rng.randint(0, L))] = -0.25
+    elif family == 8:
+        w[::2, int(rng.randint(0, L))] = float("nan")
+    elif family == 9:
+        w[::2, int(rng.randint(0, L))] = float("inf")
     return w.contiguous()
 
 
@@ -69,7 +76,14 @@ def torch_cpu_sample_pdf(bins, weights, u):
     return b0 + (u - g0) / denom * (b1 - b0), inds, cdf
 
 
-def run(cases=300, seed=0, verbose=True):
+def nan_equal(a, b):
+    """torch.equal with NaN required on the same elements."""
+    return a.shape == b.shape and bool(((a == b) | ((a != a) & (b != b))).all())
+
+
+def run(cases=300, seed=0, verbose=True, families=tuple(range(8)), draw_families=tuple(range(5))):
+    """families / draw_families: what a case draws its weight rows and its draws from.  The defaults are the finite members, picked with the
+    random stream they always were picked with: the cases of a seed do not change."""
     from uc_nerf_amd import ops
     bad, rows, torch_agrees = [], 0, 0
     t0 = time.time()
@@ -80,7 +94,7 @@ def run(cases=300, seed=0, verbose=True):
         n = int(rng.choice([1, 2, 3, 17, 64, 100, 300]))
         Lb = int(rng.choice([2, 3, 5, 8, 9, 16, 33, 63, 64, 65, 128, 129, 191, 192, 256, 513, 700]))          # bin edges
         M = int(rng.choice([1, 2, 7, 32, 33, 64, 128, 129, 192, 300]))
-        fam, ufam = int(rng.randint(0, 8)), int(rng.randint(0, 5))
+        fam, ufam = families[int(rng.randint(0, len(families)))], draw_families[int(rng.randint(0, len(draw_families)))]
         from_coarse = bool(rng.rand() < 0.3) and Lb >= 3
         merge = from_coarse or bool(rng.rand() < 0.5)
         if from_coarse:
@@ -107,8 +121,11 @@ def run(cases=300, seed=0, verbose=True):
             u = torch.rand(n, M, generator=g)
             u[:, 0] = 0.0
             u[:, -1] = 1.0 - 2.0 ** -24
-        else:
+        elif ufam == 4:
             u = torch.rand(n, 1, generator=g).expand(n, M).contiguous()
+        else:
+            u = torch.rand(n, M, generator=g)
+            u[::2, int(rng.randint(0, M))] = float("nan")
         u_full = u.expand(n, M).contiguous() if shared else u
         want_s, want_i, want_c = O.sample_pdf(bins, w, u_full)
         ts, ti, tc = torch_cpu_sample_pdf(bins, w, u_full)
@@ -118,6 +135,8 @@ def run(cases=300, seed=0, verbose=True):
             # is then whatever its binary search visits, and THAT is the definition -- the oracle's counting form is not.  The device runs the same
             # search (sample_pdf_device.h), so it is held to torch-CPU's own result here
             want_s, want_i = ts, ti
+        if fam >= 8 or ufam == 5:                                         # non-finite: the definition is what torch does with the reference's lines
+            want_s, want_i, want_c = ts, ti, tc
         tag = "case %d (seed %d): n=%d bins=%d M=%d weights %d draws %d from_coarse=%d merge=%d" % (c, s, n, Lb, M, fam, ufam, from_coarse, merge)
         zm = None
         if merge and not from_coarse:
@@ -132,21 +151,20 @@ def run(cases=300, seed=0, verbose=True):
         else:
             out = ops.sample_pdf(bins.to(DEV), w.to(DEV), u.to(DEV), z_merge=None if zm is None else zm.to(DEV), want_cdf=True, want_rank=zm is not None)
         errs = []
-        if not torch.equal(out["cdf"].cpu(), want_c):
+        if not nan_equal(out["cdf"].cpu(), want_c):
             errs.append("cdf")
         if not torch.equal(out["inds"].cpu(), want_i):
             errs.append("inds")
-        if not torch.equal(out["samples"].cpu(), want_s):
-            # NaN-aware: a NaN sample (0/0 never occurs here by construction) would compare unequal
-            errs.append("samples (max diff %.3g)" % float((out["samples"].cpu() - want_s).abs().max()))
+        if not nan_equal(out["samples"].cpu(), want_s):
+            errs.append("samples (max diff %.3g)" % float(torch.nan_to_num(out["samples"].cpu() - want_s, nan=0.0).abs().max()))
         if zm is not None:
             cat = torch.cat([want_s, zm], -1)
-            if not torch.equal(out["z_sorted"].cpu(), torch.sort(cat, -1)[0]):
+            if not nan_equal(out["z_sorted"].cpu(), torch.sort(cat, -1)[0]):
                 errs.append("z_sorted")
             rank = out["merge_rank"].cpu().long()
             if not torch.equal(torch.sort(rank, -1)[0], torch.arange(cat.shape[1]).expand_as(rank)):
                 errs.append("merge_rank is not a permutation")
-            elif not torch.equal(torch.zeros_like(cat).scatter_(-1, rank, cat), out["z_sorted"].cpu()):
+            elif not nan_equal(torch.zeros_like(cat).scatter_(-1, rank, cat), out["z_sorted"].cpu()):
                 errs.append("merge_rank does not place cat into z_sorted")
         rows += n
         if errs:

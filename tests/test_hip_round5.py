@@ -480,6 +480,11 @@ def test_differential_fuzz_of_the_resampling_launch():
     s = fuzz_sampling.run(cases=80, seed=5, verbose=False)
     assert not s["failures"], s["failures"]
     assert s["rows"] > 3000
+    # ... and 24 more from the non-finite members (a NaN weight, a +inf weight, a NaN draw, each alone and with the finite families around it),
+    # held to the same lines run by torch on the CPU: NaN on the same elements, z_sorted with NaN last, merge_rank a permutation
+    for kw in (dict(families=(8, 9)), dict(draw_families=(5,)), dict(families=(0, 3, 8, 9), draw_families=(0, 1, 5))):
+        s = fuzz_sampling.run(cases=8, seed=6, verbose=False, **kw)
+        assert not s["failures"], s["failures"]
 
 
 def test_differential_fuzz_of_the_backward_against_oracle_autograd():

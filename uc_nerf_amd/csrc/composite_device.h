@@ -73,7 +73,7 @@ __device__ __forceinline__ Sample load_sample(const ucnerf_composite_params& p, 
         float dist = (i + 1 < p.S ? z[i + 1] - z[i] : 1e10f) * dnorm;
         float sg = raw.w + (p.noise ? p.noise[(size_t)ray * p.S + i] : 0.f);
         s.r = 1.f / (1.f + expf(-raw.x)); s.g = 1.f / (1.f + expf(-raw.y)); s.b = 1.f / (1.f + expf(-raw.z));
-        s.ex = expf(-fmaxf(sg, 0.f) * dist);
+        s.ex = expf(-(sg <= 0.f ? 0.f : sg) * dist);      // relu as torch has it: a NaN density stays NaN (fmaxf would return the 0)
         s.alpha = 1.f - s.ex;
     }
     s.f = 1.f - s.alpha + 1e-10f;

@@ -822,7 +822,10 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int e = 0; e < 8; ++e) fsec[q][e] = nfs[q][e];
-        ustash_w[opaque(lane)] = 1.f - nconf;                             // u: only needed again at the very end of the tile
+        // u: only needed again at the very end of the tile.  A sample whose point is not finite gets a NaN here (0 * NaN, 0 * inf; a finite point
+        // adds a zero): the ReLUs below are fmaxf(x, 0), which returns the 0 for a NaN, so the trunk would hand such a sample finite outputs where
+        // the reference's relu keeps the NaN of its encoding through every layer -- through u all four outputs of the sample are NaN as there
+        ustash_w[opaque(lane)] = 1.f - nconf + (0.f * npx[0] + 0.f * npx[1] + 0.f * npx[2]);
 
         // ---- point encoding -> fragments in LDS (layer 0 and the skip connection read them from there); FUSED: done at the previous tail
         if (!FUSED) {
@@ -1083,7 +1086,8 @@ __global__ void __launch_bounds__(64 * BW, UCNERF_BF16_WPS) mlp_fwd_bf16_kernel(
         out.x = 1.f / (1.f + expf(-(base.x * omu + adapt.x * u)));
         out.y = 1.f / (1.f + expf(-(base.y * omu + adapt.y * u)));
         out.z = 1.f / (1.f + expf(-(base.z * omu + adapt.z * u)));
-        out.w = fmaxf(adapt.w * omu + base.w * u, 0.f);
+        const float dens = adapt.w * omu + base.w * u;
+        out.w = dens != dens ? dens : fmaxf(dens, 0.f);                  // (relu that keeps the NaN of such a sample)
         if (h == 0 && s_raw < s_lim) reinterpret_cast<f32x4*>(p.raw)[s_raw] = out;
     }
 #if UCNERF_SPLIT_GUARD

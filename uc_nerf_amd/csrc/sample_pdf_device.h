@@ -136,9 +136,9 @@ __device__ __forceinline__ void sample_pdf_ray(const ucnerf_sample_pdf_params& p
     for (int m = lane; m < M; m += 64) {
         const float u = ur[m];
         int lo = 0, hi = L;                          // first index with cdf[idx] > u  (right=True)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (cdf[mid] <= u) lo = mid + 1; else hi = mid;
+        while (lo < hi) {                            // ATen's upper bound steps on !(mid_val > val), not on mid_val <= val: the two differ when
+            const int mid = (lo + hi) >> 1;          // either side is NaN, and inds is torch's only with the former
+            if (!(cdf[mid] > u)) lo = mid + 1; else hi = mid;
         }
         const int below = lo - 1 > 0 ? lo - 1 : 0;
         const int above = lo < L - 1 ? lo : L - 1;
@@ -164,7 +164,11 @@ __device__ __forceinline__ void sample_pdf_ray(const ucnerf_sample_pdf_params& p
         pdf_sync<WAVE_ONLY>();
         float* dst = p.z_sorted + (size_t)ray * tot_n;
         bool sorted = true;
-        for (int i = lane; i < tot_n - 1; i += 64) sorted = sorted && (i == M - 1 || srt[i] <= srt[i + 1]);
+        // (a NaN sends the row to the counting branch: srt[i] <= srt[i + 1] is false with one on either side, and the pair across the two lists,
+        // which need not be ordered, is tested for NaN alone -- with a one-element list that pair is the only one its element sits in.  The
+        // binary searches below therefore never see a NaN and need no rule for it.)
+        for (int i = lane; i < tot_n - 1; i += 64)
+            sorted = sorted && (i == M - 1 ? (srt[i] == srt[i] && srt[i + 1] == srt[i + 1]) : srt[i] <= srt[i + 1]);
         if (__all(sorted)) {
             for (int i = lane; i < tot_n; i += 64) {
                 const float x = srt[i];
@@ -196,6 +200,18 @@ __device__ __forceinline__ void sample_pdf_ray(const ucnerf_sample_pdf_params& p
 #pragma unroll
                     for (int e = 0; e < 4; ++e) rank[e] += (v < x[e]) || (v == x[e] && jj < id[e]);
                 }
+                // NaN goes last, as torch.sort puts it: both comparisons above are false for it on either side, so a non-NaN element has
+                // its rank among the non-NaN ones already and a NaN element has 0.  The latter gets the number of non-NaN elements plus the
+                // NaN ones before it; with that the ranks are a permutation for any input and every slot of z_sorted is written.
+                bool x_nan = false;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x_nan = x_nan || x[e] != x[e];
+                if (__any(x_nan))
+                    for (int jj = 0; jj < tot_n; ++jj) {
+                        const float v = srt[jj];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) rank[e] += x[e] != x[e] && (v == v || jj < id[e]);
+                    }
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (id[e] < tot_n) {
