@@ -1666,6 +1666,64 @@ struct ucnerf_bn_bwd_apply_groups_params {
 typedef struct ucnerf_bn_bwd_apply_groups_params ucnerf_bn_bwd_apply_groups_params;
 int ucnerf_bn_bwd_apply_groups(const ucnerf_bn_bwd_apply_groups_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * f4   the colour frames' resize on the device -- `PIL.Image.open(f).resize(self.img_wh, PIL.Image.BILINEAR)` of data/scared.py:450-451,
+ *      data/hamlyn.py:507-508 and data/finetune.py:445-446, with Pillow's bits: ImagingResample for 8-bit channels, box=None, reducing_gap=None
+ *      (compared byte for byte with Pillow 12.2.0; no other version was checked).  (Added to ABI v6; nothing above moved.  Struct declared with a
+ *      tag: mirrored in _lib.ADDED_STRUCTS.)
+ *
+ *   Per axis, `in` input and `out` output pixels, everything in double (the library is built with -ffp-contract=off: nothing is fused):
+ *     scale = in / out;  fs = max(scale, 1.0);  support = 1.0 * fs;  ksize = (int)ceil(support) * 2 + 1
+ *     for xx in 0 .. out-1:
+ *       center = (xx + 0.5) * scale
+ *       start  = max((int)(center - support + 0.5), 0)                 (C truncation)
+ *       count  = min((int)(center + support + 0.5), in) - start
+ *       w[x]   = tri((x + start - center + 0.5) * (1.0 / fs)), x < count;  tri(a) = 1 - |a| where |a| < 1, else 0
+ *       ww     = w[0] + w[1] + ... in ascending x;  w[x] /= ww where ww != 0
+ *       k[x]   = (int)(0.5 + w[x] * 4194304.0)  (-0.5 for a negative w, which a triangle never gives);  k[count .. ksize-1] = 0
+ *   A pass along an axis, per channel, 32-bit integer accumulator:  out[xx] = clip8((2^21 + sum_x in[start + x] * k[x]) >> 22).
+ *   The HORIZONTAL pass runs first and its result is rounded and clipped to uint8; the VERTICAL pass runs on those bytes.  A pass along an axis
+ *   whose size does not change is a copy (which is also what its coefficients give: one tap of 2^22).
+ *
+ *   ucnerf_resize_bilinear_ksize / _coeffs are host arithmetic: no device call, no allocation.  _coeffs writes start [out], count [out] and
+ *   k [out][ksize] into the caller's memory and returns ksize.  Both return UCNERF_EINVAL for a size outside 1 .. 2^24 (or a NULL array).
+ *
+ *   ucnerf_resize_bilinear_u8: N frames in ONE launch, both passes; the uint8 intermediate lives in LDS only; integer arithmetic only.
+ *     src   uint8, frame f at byte f * src_frame_stride, [Hin,Win,3] interleaved; 4-byte aligned (its bytes are read as whole dwords; the last,
+ *           partial dword of the array is read byte by byte), src_frame_stride >= 3 Hin Win
+ *     dst   uint8, frame f at byte f * dst_frame_stride, [H,W,3]; 4-byte aligned, dst_frame_stride >= 3 H W and a multiple of 4 (DeviceScene's
+ *           padded storage).  The bytes between 3 H W and the stride are NOT written.
+ *     start_x, count_x [W], k_x [W][ksize_x]: the coefficients of (Win, W) in DEVICE memory; start_y, count_y [H], k_y [H][ksize_y] those of
+ *           (Hin, H).  Tables that are not the ones _coeffs gives cannot make the kernel read or write outside src / dst (every start and count is
+ *           clamped into the tile a workgroup staged); the values are then unspecified.
+ *   UCNERF_EINVAL before any launch: NULL params or array, N < 0, N > 65535, a size outside 1 .. 32768 or 3 Hin Win / 3 H W >= 2^31, a stride
+ *   below its frame, a dst stride that is no multiple of 4, a misaligned src / dst, a ksize that is not the one the sizes imply, and an axis
+ *   with in > UCNERF_RESIZE_MAX_RATIO * out: a workgroup stages the input rows and columns its 8 x 32 output tile reads, and up to that ratio the
+ *   stage, the intermediate and the tile's coefficients fit in 64 KB of LDS.  N == 0 is legal and launches nothing.
+ *   Bound: the HBM read of the native frames (3 N Hin Win bytes in, 3 N H W out). */
+#define UCNERF_RESIZE_MAX_RATIO 16
+struct ucnerf_resize_params {
+    int32_t N;                 /* frames */
+    int32_t Hin, Win;          /* native size */
+    int32_t H, W;              /* output size */
+    int32_t ksize_x, ksize_y;  /* ucnerf_resize_bilinear_ksize(Win, W), (Hin, H) */
+    int32_t reserved;          /* 0 */
+    int64_t src_frame_stride;  /* bytes between frames */
+    int64_t dst_frame_stride;
+    const uint8_t* src;
+    uint8_t* dst;
+    const int32_t* start_x;
+    const int32_t* count_x;
+    const int32_t* k_x;
+    const int32_t* start_y;
+    const int32_t* count_y;
+    const int32_t* k_y;
+};
+typedef struct ucnerf_resize_params ucnerf_resize_params;
+int ucnerf_resize_bilinear_ksize(int in, int out);
+int ucnerf_resize_bilinear_coeffs(int in, int out, int32_t* start, int32_t* count, int32_t* k);
+int ucnerf_resize_bilinear_u8(const ucnerf_resize_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -302,6 +302,12 @@ class SampleAssembleParams(C.Structure):
                 ("intrinsics", vp), ("affine_mat", vp), ("affine_mat_inv", vp), ("proj_mats", vp), ("near_fars", vp), ("view_ids_out", vp)]
 
 
+class ResizeParams(C.Structure):
+    _fields_ = [("N", i32), ("Hin", i32), ("Win", i32), ("H", i32), ("W", i32), ("ksize_x", i32), ("ksize_y", i32), ("reserved", i32),
+                ("src_frame_stride", C.c_int64), ("dst_frame_stride", C.c_int64), ("src", vp), ("dst", vp), ("start_x", vp), ("count_x", vp),
+                ("k_x", vp), ("start_y", vp), ("count_y", vp), ("k_y", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -357,7 +363,7 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams,
                  "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
                  "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams,
-                 "ucnerf_sample_assemble_params": SampleAssembleParams}
+                 "ucnerf_sample_assemble_params": SampleAssembleParams, "ucnerf_resize_params": ResizeParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -476,6 +482,10 @@ SYMBOLS = {
     "ucnerf_depth_colormap": (C.c_int, [_P, _P]),
     # one sample of the dataset out of a device-resident scene (additive to ABI v6)
     "ucnerf_sample_assemble": (C.c_int, [_P, _P]),
+    # Pillow's BILINEAR resize of the colour frames: coefficient tables on the host, both passes in one launch (additive to ABI v6)
+    "ucnerf_resize_bilinear_ksize": (C.c_int, [C.c_int, C.c_int]),
+    "ucnerf_resize_bilinear_coeffs": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
+    "ucnerf_resize_bilinear_u8": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

@@ -451,6 +451,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_conv2d_wgrad_params); SZ(ucnerf_conv2d_dgrad_s2_params); SZ(ucnerf_conv2d_bias_grad_params);
     SZ(ucnerf_bn_stats_groups_params); SZ(ucnerf_bn_apply_groups_params); SZ(ucnerf_bn_bwd_reduce_groups_params); SZ(ucnerf_bn_bwd_apply_groups_params);
     SZ(ucnerf_sample_assemble_params);
+    SZ(ucnerf_resize_params);
 #undef SZ
     return -1;
 }

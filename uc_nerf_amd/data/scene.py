@@ -5,8 +5,10 @@ Normalize, four cv2 resizes of the sparse maps, 3 V projection matrices and thei
 at batch_size=1 and copies it to the device.  Almost all of that is constant per FRAME.  `DeviceScene` computes the per-frame part once, on the
 host, with the reference's own calls (so the bits agree), uploads it once, and leaves one launch per sample (`ops.sample_assemble`).
 
-Still the caller's job: decoding the files (JPEG / PNG / .npz) and the bilinear resize to `img_wh`.  They happen once per frame and need
-PIL / cv2, which this package does not depend on.
+The colour frames' resize to `img_wh` is built as well: `DeviceScene.from_native` takes the decoded frames at their native size and runs the
+reference's `PIL.Image.resize(img_wh, PIL.Image.BILINEAR)` on the device, with Pillow's bits (`ops.resize_bilinear_u8`; compared byte for byte
+with Pillow 12.2.0).  Still the caller's job: decoding the files (JPEG / PNG / .npz), and the two cv2 resizes of the float maps (`dpt`,
+`depths_h`), which cannot be verified without OpenCV: those two arrive at `img_wh`.
 
 Two documented differences from the reference's sample:
   * every floating tensor is float32 (numpy's `np.zeros` maps come through the reference's collation as float64);
@@ -120,6 +122,16 @@ class DeviceScene:
         N, H, W = consts["depth_img"].shape
         if frames.dtype != np.uint8 or frames.shape != (N, H, W, 3):
             raise ValueError("DeviceScene: frames must be uint8 [%d,%d,%d,3], got %s %s" % (N, H, W, frames.dtype, frames.shape))
+        self._init_resident(consts, dpt, depths_h, poses, device, scan, mean, std)
+        # the bytes are read as dwords, four pixels to a thread: every frame starts on a dword
+        stride = (3 * H * W + 3) // 4 * 4
+        padded = np.zeros((N, stride), np.uint8)
+        padded[:, :3 * H * W] = frames.reshape(N, -1)
+        self.frames = torch.from_numpy(padded).to(device)
+
+    def _init_resident(self, consts, dpt, depths_h, poses, device, scan, mean, std):
+        """Everything resident but the frames."""
+        N, H, W = consts["depth_img"].shape
         dpt = np.asarray(dpt, dtype=np.float32)
         depths_h = np.zeros((N, H, W), np.float32) if depths_h is None else np.asarray(depths_h, dtype=np.float32)
         if dpt.shape != (N, H, W) or depths_h.shape != (N, H, W):
@@ -127,12 +139,7 @@ class DeviceScene:
         self.N, self.H, self.W, self.device = N, H, W, device
         self.offsets = [int(o) for o in consts["offsets"]]
         self.poses = None if poses is None else np.asarray(poses)
-        # the bytes are read as dwords, four pixels to a thread: every frame starts on a dword
-        stride = (3 * H * W + 3) // 4 * 4
-        padded = np.zeros((N, stride), np.uint8)
-        padded[:, :3 * H * W] = frames.reshape(N, -1)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)        # noqa: E731
-        self.frames = up(padded)
         self.dpt, self.depths_h = up(dpt), up(depths_h)
         for name in ("depth_img", "weight_img", "kp_depth", "kp_weight", "kp_coord", "row1", "col1", "row2", "col2",
                      "c2w", "w2c", "intrinsic", "affine", "affine_inv", "ref_proj_inv"):
@@ -157,6 +164,58 @@ class DeviceScene:
         """record: `formats.load_poses_bounds`'s; sparse: `formats.colmap_sparse_depth`'s per-frame list (image-name order); frames uint8
         [N,H,W,3] already at img_wh = (W, H); dpt float32 [N,H,W] already resized; depths_h float32 [N,H,W] or None (zeros)."""
         return cls.from_arrays(record["poses"], record["focal"], record["bounds"], sparse, frames, dpt, depths_h, img_wh, device, scan)
+
+    @classmethod
+    def from_native(cls, poses, focal, bounds, sparse, frames, dpt, depths_h=None, img_wh=None, batch=32, device="cuda", scan=0):
+        """As `from_arrays`, from frames at their NATIVE size: `frames` is an iterable of decoded uint8 arrays [h, w, 3] (sizes may differ between
+        frames), and every one goes through the reference's `PIL.Image.resize(img_wh, PIL.Image.BILINEAR)` on the device, bit for bit
+        (`ops.resize_bilinear_u8`).  Consecutive frames of equal shape are uploaded and resized `batch` at a time, straight into the resident padded
+        storage: no full-size copy of the scene is ever resident, on either side.  `img_wh` = (W, H) is required; `dpt` and `depths_h` are already
+        at `img_wh`, as in `from_arrays`.  There is no host route: `device` must be a ROCm device.  `sample()` is the same code on the result."""
+        from .. import ops
+        if img_wh is None:
+            raise ValueError("DeviceScene.from_native: img_wh = (W, H) is required (the frames come at their native size)")
+        W, H = int(img_wh[0]), int(img_wh[1])
+        if W < 1 or H < 1:
+            raise ValueError("DeviceScene.from_native: img_wh = %r" % (tuple(img_wh),))
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("DeviceScene.from_native: batch = %d, expected at least 1" % batch)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("DeviceScene.from_native: the resize runs on a ROCm device, got device=%s (there is no host route)" % device)
+        self = cls.__new__(cls)
+        self._init_resident(scene_constants(poses, focal, bounds, sparse, (W, H)), dpt, depths_h, poses, device, scan, MEAN, STD)
+        N = self.N
+        self.frames = torch.zeros((N, (3 * H * W + 3) // 4 * 4), dtype=torch.uint8, device=device)
+        done, group = 0, []
+
+        def flush():
+            nonlocal done
+            if group:
+                src = torch.from_numpy(np.stack(group)).to(device)
+                ops.resize_bilinear_u8(src, (W, H), out=self.frames[done:done + len(group)])
+                done += len(group)
+                del group[:]
+
+        for i, fr in enumerate(frames):
+            fr = np.asarray(fr)
+            if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3 or fr.shape[0] < 1 or fr.shape[1] < 1:
+                raise ValueError("DeviceScene.from_native: frame %d must be uint8 [h,w,3], got %s %s" % (i, fr.dtype, fr.shape))
+            if i >= N:
+                raise ValueError("DeviceScene.from_native: more than the %d frames the poses give" % N)
+            if group and (len(group) == batch or group[0].shape != fr.shape):
+                flush()
+            group.append(fr)
+        flush()
+        if done != N:
+            raise ValueError("DeviceScene.from_native: %d frames, %d poses" % (done, N))
+        return self
+
+    @classmethod
+    def from_native_records(cls, record, sparse, frames, dpt, depths_h=None, img_wh=None, batch=32, device="cuda", scan=0):
+        """`from_native` with `formats.load_poses_bounds`'s record, as `from_records` is to `from_arrays`."""
+        return cls.from_native(record["poses"], record["focal"], record["bounds"], sparse, frames, dpt, depths_h, img_wh, batch, device, scan)
 
     def n_keypoints(self, frame):
         return self.offsets[frame + 1] - self.offsets[frame]

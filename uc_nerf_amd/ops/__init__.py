@@ -30,5 +30,5 @@ from .metrics import (PackedConv, _eval_workspace, _is_cell, colormap_table, con
 from .cnn import (BN_MAX_GROUPS, PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _Conv2dTrain, _Conv3dBnTrain, _Conv3dTrain, batch_norm_train,  # noqa: F401
                   batch_norm_train_bwd, conv2d_bias_grad, conv2d_bn_train, conv2d_dgrad, conv2d_dgrad_pack, conv2d_train, conv2d_wgrad,
                   conv3d, conv3d_bn_train, conv3d_dgrad, conv3d_dgrad_pack, conv3d_pack, conv3d_train, conv3d_wgrad)
-from .data import SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, sample_assemble      # noqa: F401
+from .data import RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, resize_bilinear_u8, resize_coeffs, sample_assemble      # noqa: F401
 from .render import RenderPass      # noqa: F401

@@ -1,11 +1,15 @@
-"""The input side on the device: one sample of the reference's dataset assembled from a resident scene in one launch."""
+"""The input side on the device: one sample of the reference's dataset assembled from a resident scene in one launch, and Pillow's BILINEAR
+resize of the decoded colour frames (bit for bit) that fills such a scene from frames at their native size."""
+import ctypes as C
+
 import torch
 
 from .. import _lib as L
-from ._core import _launch, _ptr
+from ._core import _dev, _launch, _ptr
 
 SAMPLE_MAX_ROWS = 1024      # the reference's rays_depth[:1024]
 SAMPLE_MAX_VIEWS = 9        # the MLP's view_num range
+RESIZE_MAX_RATIO = 16       # UCNERF_RESIZE_MAX_RATIO: in <= 16 * out on each axis (a workgroup's tile has to fit in LDS)
 
 _RESIDENT = ("frames", "depth_img", "weight_img", "row1", "col1", "row2", "col2", "kp_depth", "kp_weight", "kp_coord",
              "c2w", "w2c", "intrinsic", "affine", "affine_inv", "ref_proj_inv")
@@ -100,3 +104,84 @@ def sample_assemble(res, view_ids, perm, n_rows, unpreprocess=False):
     if unpreprocess:
         out["images_unpre"] = seg[1].view(1, V, 3, H, W)
     return out
+
+
+def resize_coeffs(in_size, out_size):
+    """Pillow's BILINEAR coefficient table of one axis (`in_size` -> `out_size` pixels) from ucnerf_resize_bilinear_coeffs: host arithmetic in
+    double, no device.  Returns int32 CPU tensors (start [out], count [out], k [out, ksize]): output pixel xx is
+    clip8((2^21 + sum_x in[start[xx] + x] * k[xx, x]) >> 22) over x < count[xx]; k[xx, count[xx]:] is 0."""
+    in_size, out_size = int(in_size), int(out_size)
+    lib = L.lib()
+    ksize = lib.ucnerf_resize_bilinear_ksize(in_size, out_size)
+    L.check(min(ksize, 0), "ucnerf_resize_bilinear_ksize")
+    start, count = torch.empty(out_size, dtype=torch.int32), torch.empty(out_size, dtype=torch.int32)
+    k = torch.empty((out_size, ksize), dtype=torch.int32)
+    rc = lib.ucnerf_resize_bilinear_coeffs(in_size, out_size, C.c_void_p(start.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(k.data_ptr()))
+    L.check(min(rc, 0), "ucnerf_resize_bilinear_coeffs")
+    return start, count, k
+
+
+_resize_tables = {}      # (in, out, device) -> the three tables on that device
+
+
+def _device_coeffs(in_size, out_size, dev):
+    key = (in_size, out_size, str(dev))
+    t = _resize_tables.get(key)
+    if t is None:
+        t = _resize_tables[key] = tuple(a.to(dev) for a in resize_coeffs(in_size, out_size))
+    return t
+
+
+def resize_bilinear_u8(src, out_wh, out=None, out_frame_stride=None):
+    """`PIL.Image.fromarray(frame).resize(out_wh, PIL.Image.BILINEAR)` of every frame of `src`, bit for bit (Pillow 12.2.0's), in one launch on the
+    current stream: ucnerf_resize_bilinear_u8.  src: contiguous uint8 device tensor [N,Hin,Win,3]; out_wh = (W, H).  Returns a contiguous uint8
+    [N,H,W,3].  With `out` (a contiguous uint8 device tensor of N frames, `out_frame_stride` bytes apart -- default: out.shape[1] of a [N, stride]
+    tensor; a multiple of 4 and at least 3 H W, as DeviceScene's padded storage is) the frames are written there, the bytes between 3 H W and the
+    stride are left as they are, and `out` is returned.  The device coefficient tables are cached per (in, out, device).  Each axis may shrink by at
+    most RESIZE_MAX_RATIO; nothing is synchronised or read back."""
+    dev = _dev(src)
+    if src.dtype != torch.uint8:
+        raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: src must be uint8, got %s" % src.dtype)
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: src must be [N,Hin,Win,3], got %s" % (tuple(src.shape),))
+    if not src.is_contiguous():
+        raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: src must be contiguous")
+    N, Hin, Win = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    W, H = int(out_wh[0]), int(out_wh[1])
+    if W < 1 or H < 1 or Hin < 1 or Win < 1:
+        raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: %d x %d -> %d x %d (a size below 1)" % (Hin, Win, H, W))
+    frame = 3 * H * W
+    packed = None
+    if out is None:
+        stride = (frame + 3) // 4 * 4
+        buf = torch.empty((N, stride), dtype=torch.uint8, device=dev)
+        packed = buf if stride == frame else None
+        dst = buf
+    else:
+        if not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: out must be a contiguous uint8 tensor on %s" % dev)
+        if out_frame_stride is None:
+            if out.dim() != 2 or out.shape[0] != N:
+                raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: out must be [%d, frame_stride] bytes (or give out_frame_stride), got %s"
+                                   % (N, tuple(out.shape)))
+            out_frame_stride = out.shape[1]
+        stride = int(out_frame_stride)
+        if N and out.numel() < (N - 1) * stride + frame:
+            raise RuntimeError("uc_nerf_amd.resize_bilinear_u8: out holds %d bytes, %d frames of stride %d need %d"
+                               % (out.numel(), N, stride, (N - 1) * stride + frame))
+        dst = out
+    p = L.ResizeParams()
+    p.N, p.Hin, p.Win, p.H, p.W = N, Hin, Win, H, W
+    p.src_frame_stride, p.dst_frame_stride = 3 * Hin * Win, stride
+    if N:
+        sx, cx, kx = _device_coeffs(Win, W, dev)
+        sy, cy, ky = _device_coeffs(Hin, H, dev)
+        p.ksize_x, p.ksize_y = kx.shape[1], ky.shape[1]
+        p.src, p.dst = _ptr(src), _ptr(dst)
+        p.start_x, p.count_x, p.k_x, p.start_y, p.count_y, p.k_y = _ptr(sx), _ptr(cx), _ptr(kx), _ptr(sy), _ptr(cy), _ptr(ky)
+    _launch("ucnerf_resize_bilinear_u8", p, dev)
+    if out is not None:
+        return out
+    if packed is not None:
+        return packed.view(N, H, W, 3)
+    return dst[:, :frame].contiguous().view(N, H, W, 3)        # (3 H W is no multiple of 4: one device copy out of the padded rows)
