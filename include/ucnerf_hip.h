@@ -655,6 +655,10 @@ int ucnerf_composite_merged_bwd(const ucnerf_composite_merged_bwd_params* p, voi
  *      regularisation network.  (The warped-image volume of :614,617 is never used by the reference and is not built.)
  *      ucnerf_depth_regress replaces network/mvs_models.py:629-646: softmax over depth (+ optional initial logits),
  *      expected depth, 4-tap photometric confidence, cropped by `pad`.
+ *      Non-finite inputs land where torch's own ops put them: a NaN or +-inf projected coordinate picks the pixel F.grid_sample picks (NaN: index
+ *      0 of the axis; +-inf: the clamped end) and counts as outside the view; a NaN or +inf logit, or a pixel of -inf logits only, makes the
+ *      pixel's probabilities, depth AND confidence NaN (clamp(0, 1) keeps a NaN); an infinite g_variance gives inf * v_i - inf * mean per view,
+ *      the sum of the two terms autograd adds.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
     int32_t V, C, H, W;        /* source feature maps [V,C,H,W] */
@@ -740,8 +744,9 @@ int ucnerf_depth_hypotheses(const ucnerf_depth_hypotheses_params* p, void* strea
  * (CascadeMVSNet with grad_method="undetach", network/mvs_models.py:715-722; both added to ABI v6, nothing above moved).
  *
  * ucnerf_depth_regress_bwd_values: depth = sum_d prob_volume[d] * depth_values[d], cropped by `pad`, so
- *   g_depth_values[d, y + pad, x + pad] = prob_volume[d, y + pad, x + pad] * g_depth[y, x], and 0 on the border of `pad` pixels (the crop drops
- *   it); the confidence does not depend on depth_values.  Every element of g_depth_values is written.  D, Hp, Wp, pad >= 0, Hp >= 2 pad,
+ *   g_depth_values[d, y + pad, x + pad] = prob_volume[d, y + pad, x + pad] * g_depth[y, x], and prob_volume * 0 on the border of `pad` pixels
+ *   (the crop drops it: 0 for a finite probability, NaN for a NaN one, as torch's slice backward gives); the confidence does not depend on
+ *   depth_values.  Every element of g_depth_values is written.  D, Hp, Wp, pad >= 0, Hp >= 2 pad,
  *   Wp >= 2 pad, Hp * Wp < 2^31; a volume of zero elements is success, nothing launched; g_depth is read only where the cropped map is not empty.
  *
  * ucnerf_depth_hypotheses_bwd: the backward of ucnerf_depth_hypotheses in MAP mode, g_out [D, h + 2 pad, w + 2 pad] -> g_cur_depth [h0, w0],

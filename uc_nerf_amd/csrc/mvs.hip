@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(DR_PIX * DR_DL) depth_regress_kernel(ucnerf_de
         s4 += (d >= 0 && d < p.D) ? prs[d][px] : 0.f;
     }
     s4 = 4.f * (s4 / 4.f);
-    s4 = fminf(fmaxf(s4, 0.f), 1.f);
+    s4 = s4 < 0.f ? 0.f : s4 > 1.f ? 1.f : s4;          // torch.clamp(0, 1): a NaN stays (fminf / fmaxf would make it 0 next to a NaN depth)
     const int yy = (int)(t / p.Wp) - p.pad, xx = (int)(t % p.Wp) - p.pad;
     const int H = p.Hp - 2 * p.pad, W = p.Wp - 2 * p.pad;
     if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
@@ -208,9 +208,11 @@ __global__ void __launch_bounds__(256) cost_volume_bwd_kernel(ucnerf_cost_volume
             if (i < p.V) { v[i] = p.feats[i * chw + c * hw + (unsigned)idx[i]]; s = s + v[i]; }
         const float mean = s * count;
         const float g2 = live ? 2.f * count * bp.g_variance[(size_t)c * total + t] : 0.f;
+        // an infinite upstream gradient: autograd adds the two terms' gradients, inf * v_i - inf * mean (NaN where they share a sign), not inf * (v_i - mean)
+        const bool g_inf = fabsf(g2) == INFINITY;
 #pragma unroll
         for (int i = 0; i < CV_MAX_VIEWS; ++i)
-            if (i < p.V) run_atomic_add<8>(bp.g_feats + (i * chw + c * hw), live ? idx[i] : -1, g2 * (v[i] - mean), dpos);
+            if (i < p.V) run_atomic_add<8>(bp.g_feats + (i * chw + c * hw), live ? idx[i] : -1, g_inf ? g2 * v[i] - g2 * mean : g2 * (v[i] - mean), dpos);
     }
 }
 
@@ -285,7 +287,7 @@ __global__ void __launch_bounds__(DRV_BLOCK) depth_regress_bwd_values_kernel(ucn
     const int d_begin = blockIdx.y * DRV_DEPTHS, d_end = min(d_begin + DRV_DEPTHS, p.D);
     for (int d = d_begin; d < d_end; ++d) {
         const size_t at = (size_t)d * plane + t;
-        p.g_depth_values[at] = inside ? p.prob_volume[at] * g : 0.f;
+        p.g_depth_values[at] = p.prob_volume[at] * g;                         // (border: p * 0 -- 0 for a finite p, NaN for a NaN p, as the crop's backward gives)
     }
 }
 
