@@ -1729,6 +1729,45 @@ int ucnerf_resize_bilinear_ksize(int in, int out);
 int ucnerf_resize_bilinear_coeffs(int in, int out, int32_t* start, int32_t* count, int32_t* k);
 int ucnerf_resize_bilinear_u8(const ucnerf_resize_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * t1   the training step's three target gathers -- train.py:166-176: sparse_depths[:, r, c] and sparse_weights[:, r, c] over the rays from
+ *      n_rays on, dpt[:, r, c] over the patch rays, (r, c) the columns of pixel_coordinates.  ONE launch instead of torch's slices and index
+ *      kernels; the entry point does not synchronise the stream and reads nothing back.  (Added to ABI v6; nothing above moved.  Struct
+ *      declared with a tag: mirrored in _lib.ADDED_STRUCTS.)
+ *
+ *     sparse_depths, sparse_weights, dpt   [H,W] float32 maps, read in place
+ *     pixel_coordinates   [2, n_total], row 0 the image rows, row 1 the image columns; int64 (coord_is_float = 0) or float32 holding whole
+ *                         numbers (coord_is_float = 1).  Both give the same bits.
+ *     target_depths[i]  = sparse_depths[r][c], target_weights[i] = sparse_weights[r][c] at column n_rays + i,  i < n_total - n_rays
+ *     patch_dpt[j]      = dpt[r][c] at column j,  j < patch_num * patch_size^2
+ *   Indexing is torch's advanced indexing: a row in [-H, H) or a column in [-W, W) is taken, a negative one after adding H (W).  Values are
+ *   copied, never computed: every bit pattern (NaN payloads, -0.0) arrives as it is.
+ *   A coordinate outside that range -- or a float32 coordinate that is no whole number, NaN and the infinities included -- reads nothing: its
+ *   element is NaN (0x7fc00000) and one bit of *status is set with an atomic OR: bit 0 for a depth ray, bit 1 for a patch ray.  status may be
+ *   NULL (no word is kept).  The word is sticky: the entry point never clears it.  No other element is affected.
+ *   UCNERF_EINVAL before any launch: NULL params, a negative count or size, H or W above 2^24, n_total above 2^29, n_rays > n_total,
+ *   patch_num * patch_size^2 > n_total, coord_is_float outside {0, 1}; and, when there is an element to write, H or W of 0, a NULL or
+ *   misaligned pixel_coordinates, a NULL map or output of a non-empty part.  n_total == n_rays and patch_num == 0 are legal; with both, nothing
+ *   is launched.  Bound: launch latency (a few thousand floats a step). */
+struct ucnerf_step_targets_params {
+    int32_t H, W;
+    int32_t n_total;           /* columns of pixel_coordinates */
+    int32_t n_rays;            /* the depth rays are the columns n_rays .. n_total - 1 */
+    int32_t patch_num, patch_size;
+    int32_t coord_is_float;    /* 0: int64 coordinates, 1: float32 */
+    int32_t reserved;          /* 0 */
+    const float* sparse_depths;
+    const float* sparse_weights;
+    const float* dpt;
+    const void* pixel_coordinates;
+    float* target_depths;      /* [n_total - n_rays] */
+    float* target_weights;     /* [n_total - n_rays] */
+    float* patch_dpt;          /* [patch_num * patch_size^2] */
+    uint32_t* status;          /* one sticky word, or NULL */
+};
+typedef struct ucnerf_step_targets_params ucnerf_step_targets_params;
+int ucnerf_step_targets(const ucnerf_step_targets_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

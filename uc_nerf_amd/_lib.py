@@ -308,6 +308,12 @@ class ResizeParams(C.Structure):
                 ("k_x", vp), ("start_y", vp), ("count_y", vp), ("k_y", vp)]
 
 
+class StepTargetsParams(C.Structure):
+    _fields_ = [("H", i32), ("W", i32), ("n_total", i32), ("n_rays", i32), ("patch_num", i32), ("patch_size", i32), ("coord_is_float", i32),
+                ("reserved", i32), ("sparse_depths", vp), ("sparse_weights", vp), ("dpt", vp), ("pixel_coordinates", vp), ("target_depths", vp),
+                ("target_weights", vp), ("patch_dpt", vp), ("status", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -363,6 +369,7 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams,
                  "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
                  "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams,
+                 "ucnerf_step_targets_params": StepTargetsParams,
                  "ucnerf_sample_assemble_params": SampleAssembleParams, "ucnerf_resize_params": ResizeParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
@@ -486,6 +493,8 @@ SYMBOLS = {
     "ucnerf_resize_bilinear_ksize": (C.c_int, [C.c_int, C.c_int]),
     "ucnerf_resize_bilinear_coeffs": (C.c_int, [C.c_int, C.c_int, _P, _P, _P]),
     "ucnerf_resize_bilinear_u8": (C.c_int, [_P, _P]),
+    # the training step's three target gathers in one launch (additive to ABI v6)
+    "ucnerf_step_targets": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

@@ -452,6 +452,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_bn_stats_groups_params); SZ(ucnerf_bn_apply_groups_params); SZ(ucnerf_bn_bwd_reduce_groups_params); SZ(ucnerf_bn_bwd_apply_groups_params);
     SZ(ucnerf_sample_assemble_params);
     SZ(ucnerf_resize_params);
+    SZ(ucnerf_step_targets_params);
 #undef SZ
     return -1;
 }

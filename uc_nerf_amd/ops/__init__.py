@@ -4,8 +4,8 @@ PyTorch is plumbing here (device memory, streams, autograd bookkeeping); every c
 libucnerf_hip.so.  All functions require float32 tensors on a ROCm device and raise otherwise.
 
 One module per kernel family; this file only re-exports their names.  Module state (the MLP's backward mode, split operand and guard
-words in `network`, the loss words in `mvs`, build_rays_test's prepared structs in `rays`) is not re-exported: a copy here would go stale.
-Read it through its home module or the accessors (`backward_mode()`, `split_operand()`, `split_guard_status()`, `loss_status()`).
+words in `network`, the loss words in `mvs`, the target words in `data`, build_rays_test's prepared structs in `rays`) is not re-exported: a copy here would go stale.
+Read it through its home module or the accessors (`backward_mode()`, `split_operand()`, `split_guard_status()`, `loss_status()`, `step_targets_status()`).
 """
 from ._core import (Event, _NO_SWITCH, _NoSwitch, _cur_dev, _dev, _dev_as, _dev_f32, _f32, _launch, _mat, _on, _opt,  # noqa: F401
                     _ptr, _raw_stream, _stream)
@@ -30,5 +30,6 @@ from .metrics import (PackedConv, _eval_workspace, _is_cell, colormap_table, con
 from .cnn import (BN_MAX_GROUPS, PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _Conv2dTrain, _Conv3dBnTrain, _Conv3dTrain, batch_norm_train,  # noqa: F401
                   batch_norm_train_bwd, conv2d_bias_grad, conv2d_bn_train, conv2d_dgrad, conv2d_dgrad_pack, conv2d_train, conv2d_wgrad,
                   conv3d, conv3d_bn_train, conv3d_dgrad, conv3d_dgrad_pack, conv3d_pack, conv3d_train, conv3d_wgrad)
-from .data import RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, resize_bilinear_u8, resize_coeffs, sample_assemble      # noqa: F401
+from .data import (RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, _target_word, resize_bilinear_u8, resize_coeffs,  # noqa: F401
+                   sample_assemble, step_targets, step_targets_status, step_targets_status_clear)
 from .render import RenderPass      # noqa: F401

@@ -1,11 +1,12 @@
-"""The input side on the device: one sample of the reference's dataset assembled from a resident scene in one launch, and Pillow's BILINEAR
-resize of the decoded colour frames (bit for bit) that fills such a scene from frames at their native size."""
+"""The input side on the device: one sample of the reference's dataset assembled from a resident scene in one launch, Pillow's BILINEAR
+resize of the decoded colour frames (bit for bit) that fills such a scene from frames at their native size, and the training step's three
+target gathers out of such a sample's maps in one launch."""
 import ctypes as C
 
 import torch
 
 from .. import _lib as L
-from ._core import _dev, _launch, _ptr
+from ._core import _cur_dev, _dev, _launch, _ptr
 
 SAMPLE_MAX_ROWS = 1024      # the reference's rays_depth[:1024]
 SAMPLE_MAX_VIEWS = 9        # the MLP's view_num range
@@ -185,3 +186,78 @@ def resize_bilinear_u8(src, out_wh, out=None, out_frame_stride=None):
     if packed is not None:
         return packed.view(N, H, W, 3)
     return dst[:, :frame].contiguous().view(N, H, W, 3)        # (3 H W is no multiple of 4: one device copy out of the padded rows)
+
+
+# one sticky status word per device (bit 0: a depth ray, bit 1: a patch ray of some step_targets call had a coordinate outside the image),
+# allocated once and kept for the life of the process
+_target_words = {}
+
+
+def _target_word(device=None):
+    idx = _cur_dev() if device is None or torch.device(device).index is None else torch.device(device).index
+    w = _target_words.get(idx)
+    if w is None:
+        w = _target_words[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+    return w
+
+
+def step_targets_status(clear=False, device=None):
+    """The status word of `step_targets` on `device` (default: the current one) as an int: bit 0 set = a depth ray, bit 1 set = a patch ray of
+    some call since the last clear had a coordinate outside the image (its element was NaN).  SYNCHRONISES (reads the word back); clear=True
+    also zeroes it afterwards."""
+    w = _target_word(device)
+    v = int(w.item())
+    if clear:
+        w.zero_()
+    return v
+
+
+def step_targets_status_clear(device=None):
+    """Enqueues a clear of the status word on the current stream (no synchronisation)."""
+    _target_word(device).zero_()
+
+
+def _target_map(t, name, H, W, dev):
+    if not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (1, H, W)):
+        raise RuntimeError("uc_nerf_amd.step_targets: %s must be a contiguous float32 [1,%d,%d] tensor on %s (it is read in place)" % (name, H, W, dev))
+    return t
+
+
+def step_targets(sparse_depths, sparse_weights, dpt, pixel_coordinates, n_rays, patch_num, patch_size, status=None):
+    """The training step's three target gathers (train.py:166-176) in ONE launch on the current stream (ucnerf_step_targets), nothing
+    synchronised or read back, no autograd (the outputs are data):
+        target_depths  = sparse_depths[:, r[n_rays:], c[n_rays:]]        [1, n_total - n_rays]
+        target_weights = sparse_weights[:, r[n_rays:], c[n_rays:]]       [1, n_total - n_rays]
+        patch_dpt      = dpt[:, r[:P], c[:P]].reshape(-1, ps, ps, 1)     [patch_num, ps, ps, 1],  P = patch_num * ps * ps
+    with (r, c) = pixel_coordinates [2, n_total], int64 or float32 holding whole numbers (`build_rays`'s, as it returns them: no .long()).
+    The maps are contiguous float32 [1,H,W] device tensors and are read in place (`DeviceScene.sample`'s views are).  Indexing is torch's: a
+    row in [-H, H) or a column in [-W, W) wraps; the values are copied bit for bit.  A coordinate outside that range, or a float that is no
+    whole number, gives NaN in its element and sets a bit of `status` (a one-element int32 device tensor; default: the device's own word, see
+    `step_targets_status`): bit 0 for a depth ray, bit 1 for a patch ray -- torch raises a device-side assert there.  n_total == n_rays and
+    patch_num == 0 give empty tensors; with both nothing is launched."""
+    dev = _dev(sparse_depths)
+    if sparse_depths.dim() != 3:
+        raise RuntimeError("uc_nerf_amd.step_targets: sparse_depths must be [1,H,W], got %s" % (tuple(sparse_depths.shape),))
+    H, W = int(sparse_depths.shape[1]), int(sparse_depths.shape[2])
+    for t, name in ((sparse_depths, "sparse_depths"), (sparse_weights, "sparse_weights"), (dpt, "dpt")):
+        _target_map(t, name, H, W, dev)
+    pix = pixel_coordinates
+    if not (torch.is_tensor(pix) and pix.device == dev and pix.dim() == 2 and pix.shape[0] == 2 and pix.dtype in (torch.int64, torch.float32)):
+        raise RuntimeError("uc_nerf_amd.step_targets: pixel_coordinates must be an int64 or float32 [2, n_total] tensor on %s" % dev)
+    pix = pix.contiguous()
+    n_total, n_rays, patch_num, ps = int(pix.shape[1]), int(n_rays), int(patch_num), int(patch_size)
+    if status is None:
+        status = _target_word(dev)
+    elif not (torch.is_tensor(status) and status.is_cuda and status.dtype == torch.int32 and status.numel() == 1 and status.device == dev):
+        raise RuntimeError("uc_nerf_amd.step_targets: status must be a one-element int32 tensor on the maps' device")
+    p = L.StepTargetsParams()
+    p.H, p.W, p.n_total, p.n_rays, p.patch_num, p.patch_size = H, W, n_total, n_rays, patch_num, ps
+    p.coord_is_float = int(pix.dtype == torch.float32)
+    n_depth, n_patch = max(n_total - n_rays, 0), max(patch_num, 0) * max(ps, 0) ** 2
+    # (sizes the library refuses allocate nothing that matters: its check raises before anything is launched)
+    out = torch.empty(2 * n_depth + min(n_patch, n_total), device=dev)
+    t_depths, t_weights, patch = out[:n_depth], out[n_depth:2 * n_depth], out[2 * n_depth:]
+    p.sparse_depths, p.sparse_weights, p.dpt, p.pixel_coordinates = _ptr(sparse_depths), _ptr(sparse_weights), _ptr(dpt), _ptr(pix)
+    p.target_depths, p.target_weights, p.patch_dpt, p.status = _ptr(t_depths), _ptr(t_weights), _ptr(patch), _ptr(status)
+    _launch("ucnerf_step_targets", p, dev)
+    return t_depths.view(1, n_depth), t_weights.view(1, n_depth), patch.view(patch_num, ps, ps, 1)

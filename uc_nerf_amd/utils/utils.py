@@ -218,10 +218,18 @@ def build_rays(args, imgs, mvs_confidence, sparse_depths, coords, pose_ref, w2cs
                                 is_precrop_iters, ref_idx, outputs)
 
 
+def _upload(t, device):
+    """A small host tensor onto `device` without blocking the host: staged in pinned memory and copied on the current stream (the pinned block
+    is handed back to torch's host allocator only once that copy has run).  A pageable `.to(device)` would wait for the copy."""
+    if t.numel() == 0 or torch.device(device).type != "cuda":
+        return t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
 def _build_rays_fused(args, imgs, mvs_confidence, coords, pose_ref, c2ws, intrinsics, N_rays, N_samples, pad, is_precrop_iters, ref_idx, outputs):
     """The reference's draws through its own primitives, in its order and with its shapes (per half torch.multinomial, then numpy's shift pairs patch
     by patch; the uniform columns, the uniform rows; the jitter), then ONE launch (ucnerf_build_rays_train).  The picks stay on the device; the
-    host-drawn shifts and uniform pixels go up as one small tensor each."""
+    host-drawn shifts and uniform pixels go up as one small tensor each, from pinned memory, without blocking the host."""
     device = imgs.device
     H, W = imgs.shape[-2:]
     ps, half = int(args.patch_size), args.patch_num // 2
@@ -230,8 +238,8 @@ def _build_rays_fused(args, imgs, mvs_confidence, coords, pose_ref, c2ws, intrin
         sel.append(torch.multinomial(confidence.reshape(-1), half).to(device))
         shifts += [np.random.randint(0, ps) for _ in range(2 * half)]                 # (row shift, col shift) per patch
     xs, ys = _uniform_pixels(H, W, N_rays - 2 * half * ps * ps, is_precrop_iters)
-    uniform = torch.stack((xs, ys)).float().to(device)
-    shift = torch.tensor(shifts, dtype=torch.int32).reshape(-1, 2).to(device)
+    uniform = _upload(torch.stack((xs, ys)).float(), device)
+    shift = _upload(torch.tensor(shifts, dtype=torch.int32).reshape(-1, 2), device)
     n = 2 * half * ps * ps + xs.numel() + coords.shape[0]
     t_rand = torch.rand((n, N_samples), device=device)
     w2c_ref, intrinsic_ref, near_far_ref = pose_ref['w2cs'][ref_idx], pose_ref['intrinsics'][ref_idx], pose_ref['near_fars'][ref_idx]
