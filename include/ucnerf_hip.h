@@ -1768,6 +1768,72 @@ struct ucnerf_step_targets_params {
 typedef struct ucnerf_step_targets_params ucnerf_step_targets_params;
 int ucnerf_step_targets(const ucnerf_step_targets_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * d3   the batch of a FREE camera pose -- what d1 (ucnerf_sample_assemble) gives for a dataset frame, for a pose that is none: the input of a
+ *      rendered novel view.  The reference has the path helpers (utils/utils.py: gen_render_path, interp_poses) but no code that feeds such a pose
+ *      to its renderer; on the host a novel frame would cost data/scared.py:455-484's four LAPACK inverses, a get_nearest_pose_ids
+ *      (data/scared.py:69-106) and an upload.  ONE launch per novel frame; the entry point does not synchronise the stream and reads nothing
+ *      back; plain vector loads and stores, no atomics, no scratch.  (Added to ABI v6; nothing above moved.  Struct declared with a tag: mirrored
+ *      in _lib.ADDED_STRUCTS.)
+ *
+ *   Resident inputs as d1's (frames, c2w, w2c, intrinsic, affine, affine_inv of N frames of H x W pixels), and
+ *     poses        [P,3,4] camera-to-world [R | t]; pose_index selects one (a host integer: the loop counter of a path)
+ *     cand         int32 [n_cand]: the frames that may serve as sources (ids may repeat).  The list lives on the device, so the host cannot check
+ *                  it: an entry outside 0 .. N-1 is clamped into that range before it is used
+ *     intrinsic_in [3,3] or NULL (= frame 0's resident intrinsic).  ZERO SKEW IS ASSUMED: K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]
+ *   Source views: d_k = |c2w[cand[k]][:3,3] - t|^2 in float32, dx * dx, then fmaf(dy, dy, .), then fmaf(dz, dz, .).  The V - 1 smallest, in
+ *   ascending order; equal distances resolve to the lower position k in cand (stable); a NaN distance sorts after every number, by position.
+ *   This is formats.get_nearest_pose_ids with the 'dist' criterion (the square root is monotonic).  f_v = cand[k_(v-1)], v = 1 .. V-1.
+ *   Outputs, with the batch-of-one shapes of d1:
+ *     c2ws[0]  = the pose with the row 0 0 0 1;  w2cs[0] = the RIGID inverse in closed form, [R^T | -R^T t]: w2c[r][c] = R[c][r],
+ *                w2c[r][3] = -fmaf(R[2][r], t[2], fmaf(R[1][r], t[1], R[0][r] * t[0])).  Not an LU inverse: a rotation block that is not
+ *                orthonormal gives what the formula gives
+ *     intrinsics[0] = K;  K_s = K with rows 0 and 1 divided by 2^(2-s) (exact), s = 0, 1, 2
+ *     affine_mat[0][s][r][c] = fmaf(K_s[r][2], w2c[2][c], fmaf(K_s[r][1], w2c[1][c], K_s[r][0] * w2c[0][c])), r < 3; fourth row 0 0 0 1
+ *     affine_mat_inv[0][s]   = c2w . diag(K_s^-1, 1) with the analytic K_s^-1 of a zero-skew K:  [r][0] = R[r][0] / fx_s,  [r][1] = R[r][1] / fy_s,
+ *                [r][2] = fmaf(-R[r][1], cy_s / fy_s, fmaf(-R[r][0], cx_s / fx_s, R[r][2])),  [r][3] = t[r];  fourth row 0 0 0 1
+ *                (IEEE divisions; not a general 4 x 4 inverse)
+ *     proj_mats[0] = the first three rows of the identity;  proj_mats[v] = (affine[f_v][2] @ affine_mat_inv[0][2])[:3], d1's order: fmaf over
+ *                k = 0 .. 3 ascending from a first product
+ *     slots v >= 1 of c2ws, w2cs, intrinsics, affine_mat, affine_mat_inv: the rows of frame f_v, bit for bit;  near_fars[v] = (near, far), all v
+ *     view_ids_out = (-1, f_1, .., f_(V-1)) int64
+ *     images[v], images_unpre[v] for v >= 1: frame f_v through d1's expressions (the same bits);  slot 0 of both: 0.0f everywhere (a free pose
+ *                has no ground truth; nothing on the render path reads slot 0).  images_unpre may be NULL: not written
+ *   UCNERF_EINVAL before any launch: NULL params, a negative count or size, P <= 0, pose_index outside 0 .. P-1, V outside 2..9, n_cand < V,
+ *   n_cand > 4096, N outside 1..2^20, H W outside 1..2^24, frame_stride too small or not a multiple of 4, a NULL required pointer, a misaligned one.
+ *   Bound: latency ((V - 1) H W 3 bytes in, 4 to 8 times V H W 3 bytes out; every workgroup of slots 1 .. V-1 repeats the selection). */
+struct ucnerf_novel_assemble_params {
+    int32_t N, H, W, V;
+    int32_t frame_stride;      /* bytes between frames */
+    int32_t P;                 /* poses */
+    int32_t pose_index;
+    int32_t n_cand;
+    float mean[3], std[3];     /* Normalize's */
+    float unpre_mean[3], unpre_std[3];
+    float near_far[2];
+    const uint8_t* frames;
+    const float* c2w;
+    const float* w2c;
+    const float* intrinsic;
+    const float* affine;
+    const float* affine_inv;
+    const float* poses;        /* [P,3,4] */
+    const int32_t* cand;       /* [n_cand] */
+    const float* intrinsic_in; /* [3,3], or NULL */
+    float* images;             /* [V,3,H,W] */
+    float* images_unpre;       /* [V,3,H,W], or NULL */
+    float* c2ws;               /* [V,4,4] */
+    float* w2cs;
+    float* intrinsics;         /* [V,3,3] */
+    float* affine_mat;         /* [V,3,4,4] */
+    float* affine_mat_inv;
+    float* proj_mats;          /* [V,3,4] */
+    float* near_fars;          /* [V,2] */
+    int64_t* view_ids_out;     /* [V] */
+};
+typedef struct ucnerf_novel_assemble_params ucnerf_novel_assemble_params;
+int ucnerf_novel_assemble(const ucnerf_novel_assemble_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -314,6 +314,14 @@ class StepTargetsParams(C.Structure):
                 ("target_weights", vp), ("patch_dpt", vp), ("status", vp)]
 
 
+class NovelAssembleParams(C.Structure):
+    _fields_ = [("N", i32), ("H", i32), ("W", i32), ("V", i32), ("frame_stride", i32), ("P", i32), ("pose_index", i32), ("n_cand", i32),
+                ("mean", f32 * 3), ("std", f32 * 3), ("unpre_mean", f32 * 3), ("unpre_std", f32 * 3), ("near_far", f32 * 2), ("frames", vp),
+                ("c2w", vp), ("w2c", vp), ("intrinsic", vp), ("affine", vp), ("affine_inv", vp), ("poses", vp), ("cand", vp), ("intrinsic_in", vp),
+                ("images", vp), ("images_unpre", vp), ("c2ws", vp), ("w2cs", vp), ("intrinsics", vp), ("affine_mat", vp), ("affine_mat_inv", vp),
+                ("proj_mats", vp), ("near_fars", vp), ("view_ids_out", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -369,7 +377,7 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_conv2d_bias_grad_params": Conv2dBiasGradParams,
                  "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
                  "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams,
-                 "ucnerf_step_targets_params": StepTargetsParams,
+                 "ucnerf_step_targets_params": StepTargetsParams, "ucnerf_novel_assemble_params": NovelAssembleParams,
                  "ucnerf_sample_assemble_params": SampleAssembleParams, "ucnerf_resize_params": ResizeParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
@@ -495,6 +503,8 @@ SYMBOLS = {
     "ucnerf_resize_bilinear_u8": (C.c_int, [_P, _P]),
     # the training step's three target gathers in one launch (additive to ABI v6)
     "ucnerf_step_targets": (C.c_int, [_P, _P]),
+    # the batch of a free camera pose: matrices in closed form, the nearest source views picked on the device (additive to ABI v6)
+    "ucnerf_novel_assemble": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

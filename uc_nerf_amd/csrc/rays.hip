@@ -453,6 +453,7 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_sample_assemble_params);
     SZ(ucnerf_resize_params);
     SZ(ucnerf_step_targets_params);
+    SZ(ucnerf_novel_assemble_params);
 #undef SZ
     return -1;
 }

@@ -254,6 +254,31 @@ class DeviceScene:
             out["images_unpre"] = o["images_unpre"]
         return out
 
+    def sample_pose(self, poses, index, n_views, candidates=None, intrinsic=None, unpreprocess=False):
+        """The batch of a FREE camera pose, `poses[index]`, from one launch (`ops.novel_assemble`): what a rendered novel view starts from.
+        poses: contiguous float32 device tensor [P,3,4], camera-to-world (upload a path once, then loop `index`); n_views: views of the batch,
+        the pose and its n_views - 1 nearest source frames, picked ON THE DEVICE among `candidates` by camera-centre distance
+        (`formats.get_nearest_pose_ids`'s criterion; ties to the earlier candidate, NaN last).  candidates: an int32 device tensor (used as it
+        is), or a sequence of frame ids (uploaded by this call: one blocking copy), or None = the training index of `metas()` at its default
+        sample_rate, uploaded once and kept on the object.  At least n_views candidates are needed.  intrinsic: float32 device [3,3] with zero
+        skew, default frame 0's.
+        -> images [1,V,3,H,W] (slot 0 all zeros: there is no ground truth; nothing on the render path reads it), w2cs, c2ws [1,V,4,4],
+        near_fars [1,1,V,2], proj_mats [1,V,3,4], intrinsics [1,V,3,3], view_ids [1,V] int64 (slot 0 is -1), affine_mat, affine_mat_inv
+        [1,V,3,4,4], scan [1]; with unpreprocess=True also images_unpre.  No depths_h, dpt, sparse_* or rays_depth: a free pose has none.
+        Slot 0's w2c and affine_mat_inv are closed-form RIGID inverses of the pose given, not LU inverses: a rotation block that is not
+        orthonormal gives what the formulas give.  No host arithmetic on matrices, no synchronisation, nothing read back; the ids of the
+        selected frames exist only on the device."""
+        from .. import ops
+        if candidates is None:
+            candidates = getattr(self, "_train_candidates", None)
+            if candidates is None:
+                candidates = self._train_candidates = torch.from_numpy(np.arange(self.N, dtype=np.int32)[1::2].copy()).to(self.device)
+        elif not torch.is_tensor(candidates):
+            candidates = torch.from_numpy(np.ascontiguousarray(np.asarray(candidates), dtype=np.int32)).to(self.device)
+        o = ops.novel_assemble(self, poses, index, candidates, n_views, intrinsic=intrinsic, unpreprocess=unpreprocess)
+        o["scan"] = self.scan
+        return o
+
     def metas(self, split, n_views, sample_rate=2, num_samples=200, rng=None):
         """The (target, src_views) list of the reference's build_metas (data/scared.py:248-273).  Frames sample_rate // 2 :: sample_rate are the
         train index, the others the test index.  "train": `num_samples` entries; before each one `rng.shuffle` is applied to the train index in

@@ -30,6 +30,6 @@ from .metrics import (PackedConv, _eval_workspace, _is_cell, colormap_table, con
 from .cnn import (BN_MAX_GROUPS, PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _Conv2dTrain, _Conv3dBnTrain, _Conv3dTrain, batch_norm_train,  # noqa: F401
                   batch_norm_train_bwd, conv2d_bias_grad, conv2d_bn_train, conv2d_dgrad, conv2d_dgrad_pack, conv2d_train, conv2d_wgrad,
                   conv3d, conv3d_bn_train, conv3d_dgrad, conv3d_dgrad_pack, conv3d_pack, conv3d_train, conv3d_wgrad)
-from .data import (RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, _target_word, resize_bilinear_u8, resize_coeffs,  # noqa: F401
-                   sample_assemble, step_targets, step_targets_status, step_targets_status_clear)
+from .data import (NOVEL_MAX_CAND, RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, _target_word, novel_assemble,  # noqa: F401
+                   resize_bilinear_u8, resize_coeffs, sample_assemble, step_targets, step_targets_status, step_targets_status_clear)
 from .render import RenderPass      # noqa: F401

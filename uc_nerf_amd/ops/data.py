@@ -107,6 +107,72 @@ def sample_assemble(res, view_ids, perm, n_rows, unpreprocess=False):
     return out
 
 
+NOVEL_MAX_CAND = 4096       # candidates of one novel_assemble call (every workgroup of a source slot ranks them all)
+_NOVEL_RESIDENT = ("frames", "c2w", "w2c", "intrinsic", "affine", "affine_inv")
+
+
+def _novel_params(res):
+    """The parameter struct of `novel_assemble` for a resident scene, filled once with what does not change between poses (kept on `res`)."""
+    p = getattr(res, "_novel_params", None)
+    if p is not None:
+        return p
+    s = _sample_params(res)                                       # (its checks are this struct's checks: device, dtypes, shapes)
+    p = L.NovelAssembleParams()
+    p.N, p.H, p.W, p.frame_stride = s.N, s.H, s.W, s.frame_stride
+    for k in range(3):
+        p.mean[k], p.std[k], p.unpre_mean[k], p.unpre_std[k] = s.mean[k], s.std[k], s.unpre_mean[k], s.unpre_std[k]
+    p.near_far[0], p.near_far[1] = s.near_far[0], s.near_far[1]
+    for name in _NOVEL_RESIDENT:
+        setattr(p, name, _ptr(getattr(res, name)))
+    res._novel_params = p
+    return p
+
+
+def novel_assemble(res, poses, index, cand, V, intrinsic=None, unpreprocess=False):
+    """The batch of a FREE camera pose out of a resident scene (`uc_nerf_amd.data.DeviceScene.sample_pose` calls this): ucnerf_novel_assemble, one
+    launch on the current stream, nothing synchronised or read back.  `res` as for `sample_assemble`.  poses: contiguous float32 device tensor
+    [P,3,4], camera-to-world [R | t]; index: Python int, the pose of this call; cand: contiguous int32 device tensor [n_cand], V <= n_cand <=
+    NOVEL_MAX_CAND, the frames that may serve as sources (an entry outside 0..N-1 is clamped into that range on the device); V: views of the
+    batch, 2..SAMPLE_MAX_VIEWS -- the pose itself and its V - 1 nearest candidates (squared distance of the camera centres in float32, ascending,
+    ties to the lower position in `cand`, NaN last); intrinsic: contiguous float32 device tensor [3,3] with ZERO SKEW, default frame 0's.
+    Slot 0 carries the pose's matrices in closed form: w2cs[0] is the rigid inverse [R^T | -R^T t], affine_mat_inv[0] is c2w . diag(K_s^-1, 1)
+    -- neither is an LU inverse; a rotation block that is not orthonormal gives what the formulas give (include/ucnerf_hip.h has the fmaf orders).
+    Slots 1..V-1 are the selected frames as `sample_assemble` gives them, bit for bit, except proj_mats[v] = (affine[v][2] @ affine_mat_inv[0][2])[:3].
+    Returns a dict of device tensors, views of one allocation: images [1,V,3,H,W] (slot 0 all 0.0: a free pose has no ground truth; with
+    unpreprocess also images_unpre), c2ws / w2cs [1,V,4,4], intrinsics [1,V,3,3], affine_mat / affine_mat_inv [1,V,3,4,4], proj_mats [1,V,3,4],
+    near_fars [1,1,V,2], view_ids [1,V] int64 = (-1, selected frame ids)."""
+    p = _novel_params(res)
+    dev = res.frames.device
+    V, index = int(V), int(index)
+    if not (torch.is_tensor(poses) and poses.device == dev and poses.dtype == torch.float32 and poses.is_contiguous() and poses.dim() == 3
+            and tuple(poses.shape[1:]) == (3, 4)):
+        raise RuntimeError("uc_nerf_amd.novel_assemble: poses must be a contiguous float32 [P,3,4] tensor on %s" % dev)
+    if not (torch.is_tensor(cand) and cand.device == dev and cand.dtype == torch.int32 and cand.is_contiguous() and cand.dim() == 1):
+        raise RuntimeError("uc_nerf_amd.novel_assemble: cand must be a contiguous int32 [n_cand] tensor on %s" % dev)
+    if intrinsic is not None and not (torch.is_tensor(intrinsic) and intrinsic.device == dev and intrinsic.dtype == torch.float32
+                                      and intrinsic.is_contiguous() and tuple(intrinsic.shape) == (3, 3)):
+        raise RuntimeError("uc_nerf_amd.novel_assemble: intrinsic must be a contiguous float32 [3,3] tensor on %s" % dev)
+    H, W, HW = p.H, p.W, p.H * p.W
+    Va = min(max(V, 0), SAMPLE_MAX_VIEWS)                         # (a V the library refuses allocates nothing that matters: its check raises first)
+    img = Va * 3 * HW
+    sizes = [img, img if unpreprocess else 0, Va * 16, Va * 16, Va * 9, Va * 48, Va * 48, Va * 12, Va * 2, Va * 2]
+    offs, total = _carve(sizes)
+    buf = torch.empty(total, dtype=torch.float32, device=dev)
+    seg = [buf[o:o + n] for o, n in zip(offs, sizes)]
+    p.V, p.P, p.pose_index, p.n_cand = V, int(poses.shape[0]), index, int(cand.numel())
+    p.poses, p.cand, p.intrinsic_in = _ptr(poses), _ptr(cand), (_ptr(intrinsic) if intrinsic is not None else 0)
+    base = buf.data_ptr()
+    (p.images, p.images_unpre, p.c2ws, p.w2cs, p.intrinsics, p.affine_mat, p.affine_mat_inv, p.proj_mats, p.near_fars,
+     p.view_ids_out) = [base + 4 * o if n else 0 for o, n in zip(offs, sizes)]
+    _launch("ucnerf_novel_assemble", p, dev)
+    out = dict(images=seg[0].view(1, V, 3, H, W), c2ws=seg[2].view(1, V, 4, 4), w2cs=seg[3].view(1, V, 4, 4), intrinsics=seg[4].view(1, V, 3, 3),
+               affine_mat=seg[5].view(1, V, 3, 4, 4), affine_mat_inv=seg[6].view(1, V, 3, 4, 4), proj_mats=seg[7].view(1, V, 3, 4),
+               near_fars=seg[8].view(1, 1, V, 2), view_ids=seg[9].view(torch.int64).view(1, V))
+    if unpreprocess:
+        out["images_unpre"] = seg[1].view(1, V, 3, H, W)
+    return out
+
+
 def resize_coeffs(in_size, out_size):
     """Pillow's BILINEAR coefficient table of one axis (`in_size` -> `out_size` pixels) from ucnerf_resize_bilinear_coeffs: host arithmetic in
     double, no device.  Returns int32 CPU tensors (start [out], count [out], k [out, ksize]): output pixel xx is

@@ -236,6 +236,50 @@ class UCNeRFSystem:
         plt.savefig(f'{save_path}/{self.global_step:08d}_{self.idx:02d}.png')
         plt.close(fig)
 
+    # ------------------------------------------------------------------------------------------------ free-camera rendering (no counterpart)
+    def render_path(self, scene, poses, n_views=None, candidates=None, depth_vis=False):
+        """Renders the views of a camera path that are no frames of the dataset.  scene: a `DeviceScene`; poses: [P,3,4] camera-to-world (a
+        float32 device tensor is used as it is; anything else -- `data.paths.interp_path`'s float64 array -- is uploaded once as float32, one
+        blocking copy); n_views: default args.view_num, the pose and its n_views - 1 nearest source frames among `candidates`
+        (`DeviceScene.sample_pose`'s: default the scene's training index; a sequence is uploaded once, before the loop).
+        -> {'rgb' [P,3,H,W] in [0, 1], 'depth' [P,H,W]} (and 'depth_vis' [P,3,H,W] with depth_vis=True): device tensors, allocated once and
+        written frame by frame -- per frame `sample_pose` (one launch) then `validate.render_novel_view`, under no_grad, nothing read back.
+        The CNNs run in the mode `validation_step` runs them, train(): batch statistics, so the images agree with what validation measures.
+        UNLIKE validation_step this call leaves the model as it found it: every buffer of the consistency learner (the batch-norm running
+        statistics and num_batches_tracked) is copied on the device before the loop and copied back after it, and each module's `training`
+        flag is restored -- also when a frame raises."""
+        from .validate import render_novel_view
+        args = self.args
+        n_views = int(args.view_num if n_views is None else n_views)
+        dev = scene.frames.device
+        if not (torch.is_tensor(poses) and poses.device == dev and poses.dtype == torch.float32 and poses.is_contiguous()):
+            poses = torch.as_tensor(np.ascontiguousarray(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float32)).to(dev)
+        if candidates is not None and not torch.is_tensor(candidates):
+            candidates = torch.from_numpy(np.ascontiguousarray(np.asarray(candidates), dtype=np.int32)).to(dev)
+        P, H, W = int(poses.shape[0]), scene.H, scene.W
+        out = {'rgb': torch.empty(P, 3, H, W, device=dev), 'depth': torch.empty(P, H, W, device=dev)}
+        if depth_vis:
+            out['depth_vis'] = torch.empty(P, 3, H, W, device=dev)
+        net = self.Consist_Learner
+        flags = [(m, m.training) for n in (net, self.render_kwargs_train['network_fn']) for m in n.modules()]
+        with torch.no_grad():
+            saved = [(b, b.clone()) for b in net.buffers()]
+            try:
+                net.train()
+                for j in range(P):
+                    batch = scene.sample_pose(poses, j, n_views, candidates=candidates, unpreprocess=True)
+                    rgb, depth, vis = render_novel_view(args, batch, net, self.render_kwargs_train)
+                    out['rgb'][j].copy_(rgb)
+                    out['depth'][j].copy_(depth)
+                    if depth_vis:
+                        out['depth_vis'][j].copy_(vis)
+            finally:
+                for b, was in saved:
+                    b.copy_(was)
+                for m, was in flags:
+                    m.training = was
+        return out
+
     # ------------------------------------------------------------------------------------------------ train.py:326-402
     def on_validation_epoch_end(self):
         """-> {'val/PSNR', 'val/SSIM', 'val/LPIPS', 'val/abs_rel', 'val/sq_rel', 'val/rmse', 'val/rmse_log', 'val/a1', 'val/a2', 'val/a3'}; with

@@ -57,3 +57,29 @@ def render_validation_image(args, pose_ref, outputs, imgs_input, photo_confidenc
         log['pred_depth_vis'] = ops.depth_colormap(render_depth, table, minmax=cell, want_index=False)[1]
         log['uncertainty'] = net.forward_uncertainty(photo_confidence.reshape(1, -1, 1)).reshape(H, W)
     return log
+
+
+def render_novel_view(args, batch, network_mvs, render_kwargs, network_fn=None, cmap=None):
+    """One image of a FREE camera pose: `batch` is `DeviceScene.sample_pose(...)`'s (slot 0 the pose, slots 1.. the source views picked on the
+    device).  The cascade `network_mvs` runs on batch["images"][:, 1:] with slot 0's stage matrices as validation_step runs it (train.py:233-237;
+    the module's mode is the caller's: `UCNeRFSystem.render_path` sets the one validation uses), then `render_validation_image`'s chunk loop on
+    the un-normalised source images (batch["images_unpre"] when the batch carries it, train.py:61-70 applied here otherwise).  No gt_rgb, no
+    depth_gt: a free pose has neither.  -> (pred_rgb [3,H,W] clamped to [0, 1], pred_depth [H,W], pred_depth_vis [3,H,W]), device tensors;
+    nothing is read back."""
+    with torch.no_grad():
+        data = {k: v.float() for k, v in batch.items() if k != "scan"}
+        pose_ref = {k: data[k].squeeze() for k in ("w2cs", "intrinsics", "c2ws", "near_fars")}
+        near_fars = pose_ref["near_fars"]
+        imgs = data["images"]
+        H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
+        _, photo_confidence, _, outputs = network_mvs(imgs[:, 1:], data["affine_mat"][0], data["affine_mat_inv"][0], near_fars[0], pad=args.pad)
+        if "images_unpre" in data:
+            imgs = data["images_unpre"]
+        else:
+            dev = imgs.device
+            mean = torch.tensor([-0.485 / 0.229, -0.456 / 0.224, -0.406 / 0.225]).view(1, 1, 3, 1, 1).to(dev)
+            std = torch.tensor([1 / 0.229, 1 / 0.224, 1 / 0.225]).view(1, 1, 3, 1, 1).to(dev)
+            imgs = (imgs - mean) / std
+        log = render_validation_image(args, pose_ref, outputs, imgs[:, 1:], photo_confidence, H, W, near_fars, render_kwargs, network_fn=network_fn,
+                                      cmap=cmap)
+    return log["pred_rgb"], log["pred_depth"], log["pred_depth_vis"]
