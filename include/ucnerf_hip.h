@@ -1834,6 +1834,84 @@ struct ucnerf_novel_assemble_params {
 typedef struct ucnerf_novel_assemble_params ucnerf_novel_assemble_params;
 int ucnerf_novel_assemble(const ucnerf_novel_assemble_params* p, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * e1   multi-view depth fusion -- from per-view maps (rgb [N,3,H,W], depth [N,H,W]) to a coloured point cloud: the geometric consistency
+ *      filter of the MVSNet / CasMVSNet family and a deterministic compaction.  The reference has no fusion code: the rules below are this
+ *      project's own.  Neither entry point synchronises the stream or reads anything back; plain vector loads and stores, NO atomics: the
+ *      results are bit-identical from launch to launch.  (Added to ABI v6; nothing above moved.  Structs declared with a tag: mirrored in
+ *      _lib.ADDED_STRUCTS.)
+ *
+ * ucnerf_depth_consistency: ONE launch over all N views; a workgroup of 256 pixels lies inside one reference view r and forms r's and its
+ * sources' matrices once, in LDS.  Pixel convention of a1 (raygen_device.h): integer pixel (x, y), d_cam = ((x - K02) / K00, (y - K12) / K11, 1) d.
+ * ZERO SKEW IS ASSUMED: of an intrinsic only K00, K02, K11, K12 are read.  Of a 4 x 4 matrix only the first three rows are read.
+ *   w2cs == NULL: the RIGID inverse of c2ws, formed per workgroup as d3 forms it: w2c[r][c] = R[c][r],
+ *                 w2c[r][3] = -fmaf(R[2][r], t[2], fmaf(R[1][r], t[1], R[0][r] * t[0])).  Not an LU inverse.
+ * Arithmetic (float32, -ffp-contract=off: every fmaf is written out, every a / b is an IEEE division, sqrtf is correctly rounded):
+ *   M . (a, b, c):     row i = fmaf(M[i][2], c, fmaf(M[i][1], b, M[i][0] * a)) + M[i][3]
+ *   back(K, x, y, d):  ((x - K02) / K00 * d, (y - K12) / K11 * d, d)
+ *   proj(K, Q):        (K00 * Q.x / Q.z + K02, K11 * Q.y / Q.z + K12): product, then division, then sum
+ * The reference pixel (x, y) of view r with depth d is VALID iff d is finite and d > 0 and (conf given) conf is finite and conf >= conf_thresh.
+ * For every source slot j in ascending order, s = src_ids[r][j]; s < 0, s == r and s >= N are skipped.  With X = c2w_r . back(K_r, x, y, d):
+ *   1. Q = w2c_s . X; not consistent unless 0 < Q.z < inf
+ *   2. (u, v) = proj(K_s, Q); not consistent unless 0 <= u <= W - 1 and 0 <= v <= H - 1 (a NaN fails the comparison)
+ *   3. x0 = floor(u), a = u - x0, y0 = floor(v), b = v - y0 (exact); the four taps in the order (y0, x0), (y0, x0 + 1), (y0 + 1, x0),
+ *      (y0 + 1, x0 + 1) with weights (1 - a)(1 - b), a (1 - b), (1 - a) b, a b.  A tap whose weight is 0 is NOT READ (so u == W - 1 and
+ *      v == H - 1 read nothing outside the map); a tap with a non-zero weight whose depth is non-finite or <= 0 makes the source not
+ *      consistent; d_s = the taps' fmaf(w, depth, acc) in that order from acc = 0
+ *   4. Q' = w2c_r . (c2w_s . back(K_s, u, v, d_s)), d' = Q'.z; not consistent unless 0 < d' < inf; (x', y') = proj(K_r, Q')
+ *   5. consistent iff sqrtf(fmaf(ey, ey, ex * ex)) < pix_thresh with ex = x' - x, ey = y' - y, and fabsf(d' - d) / d < rel_thresh
+ *      (the square root of the sum of squares stands for hypot: pixel distances neither overflow nor underflow it)
+ *   count = the number of consistent sources (uint8; S <= 32);  mask = valid and count >= min_views (one byte, 0 or 1);
+ *   fused = (d + d'_1 + d'_2 + ..) / (float)(count + 1), the sum accumulated in source order; 0.0f where the reference pixel is not valid.
+ *   A rotation block that is not orthonormal gives what the formulas give.  pix_thresh / rel_thresh NaN: nothing is consistent.
+ * UCNERF_EINVAL before any launch: NULL params, a negative N, H, W or S, S > 32, H or W above 2^24 / N H W >= 2^31, a NULL required array
+ * (src_ids may be NULL when S == 0; conf and w2cs may be NULL).  N == 0, H == 0 or W == 0: success, nothing launched.
+ * Bound: latency / gather (4 taps x S sources per pixel, data-dependent footprint); streams 4 (+4) bytes in and 6 bytes out per pixel. */
+struct ucnerf_depth_consistency_params {
+    int32_t N, H, W, S;
+    int32_t min_views;
+    float pix_thresh, rel_thresh, conf_thresh;
+    const float* depth;        /* [N,H,W] */
+    const float* intrinsics;   /* [N,3,3] */
+    const float* c2ws;         /* [N,4,4] */
+    const float* w2cs;         /* [N,4,4], or NULL: the rigid inverse of c2ws */
+    const int32_t* src_ids;    /* [N,S] */
+    const float* conf;         /* [N,H,W], or NULL */
+    uint8_t* count;            /* [N,H,W] */
+    uint8_t* mask;             /* [N,H,W], 0 or 1 */
+    float* fused;              /* [N,H,W] */
+};
+typedef struct ucnerf_depth_consistency_params ucnerf_depth_consistency_params;
+int ucnerf_depth_consistency(const ucnerf_depth_consistency_params* p, void* stream);
+
+/* ucnerf_points_compact: the masked pixels as a point cloud, row k = the k-th pixel with mask != 0 in (view, y, x) order.
+ *   points[k] = c2w_n . back(K_n, x, y, fused) (world; the expressions above);  colors[k][c] = (uint8)(clamp(rgb[n][c][y][x], 0, 1) * 255.0f + 0.5f),
+ *   product then sum in float32, truncated; a NaN colour gives 0.
+ *   total (ONE int64 on the device) = the number of masked pixels, whatever `cap` is; rows k >= cap are not written.
+ * One ABI call, three kernels on the stream, a counted fixed-order scan: (1) every workgroup counts the mask bytes of its 1024 pixels into
+ * workspace[b]; (2) ONE workgroup turns the counts into exclusive offsets in place, 256 counts a pass with a running carry, and writes total;
+ * (3) every workgroup ranks its masked pixels (thread order = pixel order) from its offset and stores the rows.  No atomics.
+ * workspace: ucnerf_points_compact_workspace_bytes(N H W) bytes, 4-byte aligned (-1 for a negative count).
+ * UCNERF_EINVAL before any launch: NULL params, negative N, H, W or cap, H or W above 2^24 / N H W >= 2^31, a NULL required array (points / colors
+ * may be NULL when cap == 0), total not 8-byte aligned.  N H W == 0: total = 0 is written (a memset on the stream), nothing else. */
+int64_t ucnerf_points_compact_workspace_bytes(int64_t n_pixels);
+struct ucnerf_points_compact_params {
+    int32_t N, H, W;
+    int32_t reserved;
+    int64_t cap;               /* rows of points / colors */
+    const float* fused;        /* [N,H,W] */
+    const uint8_t* mask;       /* [N,H,W] */
+    const float* rgb;          /* [N,3,H,W] */
+    const float* intrinsics;   /* [N,3,3] */
+    const float* c2ws;         /* [N,4,4] */
+    int32_t* workspace;
+    float* points;             /* [cap,3] */
+    uint8_t* colors;           /* [cap,3] */
+    int64_t* total;            /* [1] */
+};
+typedef struct ucnerf_points_compact_params ucnerf_points_compact_params;
+int ucnerf_points_compact(const ucnerf_points_compact_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -322,6 +322,16 @@ class NovelAssembleParams(C.Structure):
                 ("proj_mats", vp), ("near_fars", vp), ("view_ids_out", vp)]
 
 
+class DepthConsistencyParams(C.Structure):
+    _fields_ = [("N", i32), ("H", i32), ("W", i32), ("S", i32), ("min_views", i32), ("pix_thresh", f32), ("rel_thresh", f32), ("conf_thresh", f32),
+                ("depth", vp), ("intrinsics", vp), ("c2ws", vp), ("w2cs", vp), ("src_ids", vp), ("conf", vp), ("count", vp), ("mask", vp), ("fused", vp)]
+
+
+class PointsCompactParams(C.Structure):
+    _fields_ = [("N", i32), ("H", i32), ("W", i32), ("reserved", i32), ("cap", C.c_int64), ("fused", vp), ("mask", vp), ("rgb", vp), ("intrinsics", vp),
+                ("c2ws", vp), ("workspace", vp), ("points", vp), ("colors", vp), ("total", vp)]
+
+
 class RenderParams(C.Structure):
     _fields_ = [("n", i32), ("S", i32), ("white_bkgd", i32), ("max_blocks", i32), ("cfg", MlpConfig), ("rays_o", vp),
                 ("rays_d", vp), ("z", vp), ("w2c_ref", f32 * 12), ("K_ref", f32 * 9), ("w2c_dir", f32 * 12),
@@ -378,6 +388,7 @@ ADDED_STRUCTS = {"ucnerf_depth_hypotheses_params": DepthHypothesesParams, "ucner
                  "ucnerf_bn_stats_groups_params": BnStatsGroupsParams, "ucnerf_bn_apply_groups_params": BnApplyGroupsParams,
                  "ucnerf_bn_bwd_reduce_groups_params": BnBwdReduceGroupsParams, "ucnerf_bn_bwd_apply_groups_params": BnBwdApplyGroupsParams,
                  "ucnerf_step_targets_params": StepTargetsParams, "ucnerf_novel_assemble_params": NovelAssembleParams,
+                 "ucnerf_depth_consistency_params": DepthConsistencyParams, "ucnerf_points_compact_params": PointsCompactParams,
                  "ucnerf_sample_assemble_params": SampleAssembleParams, "ucnerf_resize_params": ResizeParams}
 
 # every symbol include/ucnerf_hip.h declares: name -> (restype, argtypes)
@@ -505,6 +516,9 @@ SYMBOLS = {
     "ucnerf_step_targets": (C.c_int, [_P, _P]),
     # the batch of a free camera pose: matrices in closed form, the nearest source views picked on the device (additive to ABI v6)
     "ucnerf_novel_assemble": (C.c_int, [_P, _P]),
+    "ucnerf_depth_consistency": (C.c_int, [_P, _P]),
+    "ucnerf_points_compact_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ucnerf_points_compact": (C.c_int, [_P, _P]),
     "ucnerf_render_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "ucnerf_render_fused_fwd": (C.c_int, [_P, _P]),
     "ucnerf_gather_repack_floats": (C.c_int64, [_P]),

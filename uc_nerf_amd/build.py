@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libucnerf_hip.so")
-SOURCES = ["rays.hip", "gather.hip", "gather_cl.hip", "mlp.hip", "mlp_bf16.hip", "mlp_bf16_host.hip", "mlp_bwd.hip", "mlp_bwd_chain.hip", "mlp_wgrad.hip", "composite.hip", "composite_fold.hip", "sample_pdf.hip", "render.hip", "mvs.hip", "cascade.hip", "metrics.hip", "cas_loss.hip", "image.hip", "lpips.hip", "conv3d.hip", "bn.hip", "conv3d_bwd.hip", "conv2d_bwd.hip", "sample.hip", "resize.hip", "step_targets.hip", "novel.hip"]
+SOURCES = ["rays.hip", "gather.hip", "gather_cl.hip", "mlp.hip", "mlp_bf16.hip", "mlp_bf16_host.hip", "mlp_bwd.hip", "mlp_bwd_chain.hip", "mlp_wgrad.hip", "composite.hip", "composite_fold.hip", "sample_pdf.hip", "render.hip", "mvs.hip", "cascade.hip", "metrics.hip", "cas_loss.hip", "image.hip", "lpips.hip", "conv3d.hip", "bn.hip", "conv3d_bwd.hip", "conv2d_bwd.hip", "sample.hip", "resize.hip", "step_targets.hip", "novel.hip", "fusion.hip"]
 # (source, object name, extra flags): translation units built more than once with different switches.  mlp_bf16.hip holds the split-MLP kernels and the
 # table that names them (its default build: the three-term bf16 kernels); their host side, mlp_bf16_host.hip, is compiled once
 VARIANTS = [("mlp_bf16.hip", "mlp_bf16_plain.o", ["-DUCNERF_BF16_BUILD_TERMS=1"]), ("mlp_bf16.hip", "mlp_bf16_tail.o", ["-DUCNERF_BF16_BUILD_TAIL=1"]),

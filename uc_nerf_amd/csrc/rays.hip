@@ -454,6 +454,8 @@ int ucnerf_sizeof(const char* name) {
     SZ(ucnerf_resize_params);
     SZ(ucnerf_step_targets_params);
     SZ(ucnerf_novel_assemble_params);
+    SZ(ucnerf_depth_consistency_params);
+    SZ(ucnerf_points_compact_params);
 #undef SZ
     return -1;
 }

@@ -222,3 +222,51 @@ def load_checkpoint(path, network_fn=None, network_mvs=None, map_location="cpu")
     if network_fn is not None:
         network_fn.load_state_dict(ckpt["network_fn_state_dict"])
     return ckpt
+
+
+# ------------------------------------------------------------------------------------------------ point clouds
+_PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_PLY_PROPERTIES = ("property float x", "property float y", "property float z", "property uchar red", "property uchar green", "property uchar blue")
+
+
+def write_ply(path, points, colors):
+    """A coloured point cloud as binary little-endian PLY: `points` [n,3] float32 (x y z), `colors` [n,3] uint8 (red green blue); n may be 0.
+    The vertex record is 15 bytes, no padding."""
+    points, colors = np.asarray(points), np.asarray(colors)
+    if points.ndim != 2 or points.shape[1] != 3 or colors.shape != points.shape:
+        raise ValueError("write_ply: points and colors must both be [n,3], got %s and %s" % (points.shape, colors.shape))
+    if colors.dtype != np.uint8:
+        raise ValueError("write_ply: colors must be uint8, got %s" % colors.dtype)
+    n = len(points)
+    rec = np.empty(n, dtype=_PLY_VERTEX)
+    for k, name in enumerate(("x", "y", "z")):
+        rec[name] = points[:, k].astype("<f4", copy=False)
+    for k, name in enumerate(("red", "green", "blue")):
+        rec[name] = colors[:, k]
+    header = "\n".join(("ply", "format binary_little_endian 1.0", "element vertex %d" % n) + _PLY_PROPERTIES + ("end_header", ""))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_ply(path):
+    """The subset `write_ply` writes, back: -> (points float32 [n,3], colors uint8 [n,3]).  Anything else (another format line, other elements
+    or properties) is refused."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError("read_ply: %s has no end_header" % path)
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or len(lines) < 3 or not lines[2].startswith("element vertex "):
+        raise ValueError("read_ply: %s is not a binary_little_endian 1.0 vertex file" % path)
+    n = int(lines[2].split()[2])
+    if tuple(l for l in lines[3:] if l and not l.startswith("comment")) != _PLY_PROPERTIES:
+        raise ValueError("read_ply: %s declares other properties than float x y z, uchar red green blue" % path)
+    body = data[end + len(b"end_header\n"):]
+    if len(body) != n * _PLY_VERTEX.itemsize:
+        raise ValueError("read_ply: %s holds %d bytes of vertices, %d records need %d" % (path, len(body), n, n * _PLY_VERTEX.itemsize))
+    rec = np.frombuffer(body, dtype=_PLY_VERTEX, count=n)
+    points = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    colors = np.stack([rec["red"], rec["green"], rec["blue"]], 1).astype(np.uint8) if n else np.zeros((0, 3), np.uint8)
+    return points, colors

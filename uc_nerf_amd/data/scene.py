@@ -272,12 +272,39 @@ class DeviceScene:
         if candidates is None:
             candidates = getattr(self, "_train_candidates", None)
             if candidates is None:
-                candidates = self._train_candidates = torch.from_numpy(np.arange(self.N, dtype=np.int32)[1::2].copy()).to(self.device)
+                candidates = self._train_candidates = torch.from_numpy(self.train_index().astype(np.int32)).to(self.device)
         elif not torch.is_tensor(candidates):
             candidates = torch.from_numpy(np.ascontiguousarray(np.asarray(candidates), dtype=np.int32)).to(self.device)
         o = ops.novel_assemble(self, poses, index, candidates, n_views, intrinsic=intrinsic, unpreprocess=unpreprocess)
         o["scan"] = self.scan
         return o
+
+    def train_index(self, sample_rate=2):
+        """The frames of the training split (data/scared.py:248-252): sample_rate // 2 :: sample_rate; the others are the test index."""
+        return np.arange(self.N)[int(sample_rate / 2)::sample_rate]
+
+    def nearest_train_views(self, frame, n_views, sample_rate=2):
+        """The n_views - 1 training frames nearest to `frame` (`formats.get_nearest_pose_ids`), the frame itself left out: what
+        `metas("val", n_views, sample_rate)` lists for a test frame, for any frame.  Host arithmetic; needs the scene's poses."""
+        if self.poses is None:
+            raise ValueError("DeviceScene.nearest_train_views needs the poses the scene was built from")
+        train_index = self.train_index(sample_rate)
+        at = np.nonzero(train_index == int(frame))[0]
+        near = formats.get_nearest_pose_ids(self.poses[int(frame)], self.poses[train_index], n_views - 1, tar_id=int(at[0]) if len(at) else -1)
+        return [int(i) for i in train_index[near]]
+
+    def fusion_sources(self, frames, n_src):
+        """int32 [len(frames), n_src] on the device: `fusion.source_table` of these frames' poses (positions in `frames`, -1 padding), for
+        `ops.depth_consistency`.  Host arithmetic and one upload; the LAST table is kept (one entry, replaced when `frames` or `n_src`
+        change), so a repeated reconstruction of the same frames uploads nothing."""
+        from ..fusion import source_table
+        if self.poses is None:
+            raise ValueError("DeviceScene.fusion_sources needs the poses the scene was built from")
+        key = (tuple(int(f) for f in frames), int(n_src))
+        kept = getattr(self, "_fusion_sources", None)
+        if kept is None or kept[0] != key:
+            kept = self._fusion_sources = (key, torch.from_numpy(source_table(self.poses[list(key[0])], key[1])).to(self.device))
+        return kept[1]
 
     def metas(self, split, n_views, sample_rate=2, num_samples=200, rng=None):
         """The (target, src_views) list of the reference's build_metas (data/scared.py:248-273).  Frames sample_rate // 2 :: sample_rate are the
@@ -286,7 +313,7 @@ class DeviceScene:
         default_rng()), the first element is the target, the next n_views - 1 the sources.  "val": one entry per test frame with the
         n_views - 1 nearest train poses (`formats.get_nearest_pose_ids`); needs the scene's poses."""
         ids = np.arange(self.N)
-        train_index = ids[int(sample_rate / 2)::sample_rate]
+        train_index = self.train_index(sample_rate)
         test_index = np.array([i for i in ids if i not in train_index])
         out = []
         if split == "train":

@@ -32,4 +32,5 @@ from .cnn import (BN_MAX_GROUPS, PackedConv3d, PackedDgrad2d, _Conv2dBnTrain, _C
                   conv3d, conv3d_bn_train, conv3d_dgrad, conv3d_dgrad_pack, conv3d_pack, conv3d_train, conv3d_wgrad)
 from .data import (NOVEL_MAX_CAND, RESIZE_MAX_RATIO, SAMPLE_MAX_ROWS, SAMPLE_MAX_VIEWS, _target_word, novel_assemble,  # noqa: F401
                    resize_bilinear_u8, resize_coeffs, sample_assemble, step_targets, step_targets_status, step_targets_status_clear)
+from .fusion import COMPACT_BLOCK_ITEMS, COMPACT_SCAN_CHUNK, FUSION_MAX_SRC, depth_consistency, points_compact      # noqa: F401
 from .render import RenderPass      # noqa: F401

@@ -280,6 +280,69 @@ class UCNeRFSystem:
                     m.training = was
         return out
 
+    # ------------------------------------------------------------------------------------------------ reconstruction (no counterpart)
+    def _frame_maps(self, batch, depth_source):
+        """validation_step's steps on one sample (train.py:213-289; the caller holds no_grad and has set the CNNs' mode): the consistency learner,
+        then `render_validation_image`.  -> (depth [H,W], rgb [3,H,W], conf [H,W] or None) by `depth_source`."""
+        args = self.args
+        batch = {k: v for k, v in batch.items() if k not in ('scan', 'sparse_depths_ms', 'weight_ms')}
+        data_mvs, pose_ref = self.decode_batch(batch)
+        imgs = data_mvs['images']
+        near_fars = pose_ref['near_fars']
+        H, W = int(imgs.shape[-2]), int(imgs.shape[-1])
+        affine_mat, affine_mat_inv = data_mvs['affine_mat'][0], data_mvs['affine_mat_inv'][0]
+        _, photo_confidence, mvs_depth, outputs = self.Consist_Learner(imgs[:, 1:], affine_mat, affine_mat_inv, near_fars[0], pad=args.pad)
+        imgs = self._unpreprocessed(data_mvs)
+        log = render_validation_image(args, pose_ref, outputs, imgs[:, 1:], photo_confidence, H, W, near_fars, self.render_kwargs_train,
+                                      gt_rgb=imgs[0, 0])
+        if depth_source == "render":
+            return log['pred_depth'], log['pred_rgb'], None
+        # (stage 3's depth and confidence are [1,H,W] whatever args.pad is: ops.depth_regress drops the border itself)
+        return mvs_depth[0], log['gt_rgb'], photo_confidence[0]
+
+    def reconstruct(self, scene, frames=None, depth_source="render", n_src=4, **thresholds):
+        """A coloured point cloud of the scene from the depth maps of `frames` (default: every frame), fused on the device
+        (`uc_nerf_amd.fusion.fuse_views`: consistency filter, then compaction).  Per frame, validation's steps: `scene.sample(frame, its
+        view_num - 1 nearest training frames, unpreprocess=True)`, the consistency learner, `render_validation_image`.
+        depth_source="render": the rendered depth and colour (pred_depth, pred_rgb); "mvs": the cascade's stage-3 depth with its photometric
+        confidence as `conf` (so `conf_thresh` applies) and the frame's own colours (gt_rgb); not exercised with args.pad > 0.  n_src: source views per frame for the filter, the
+        nearest among `frames` themselves; **thresholds: pix_thresh, rel_thresh, conf_thresh, min_views.  The cameras are the scene's resident
+        c2w / w2c / intrinsic.  -> `fusion.PointCloud`, everything on the device: after a first call with the same frames (which uploads their
+        source table once: `DeviceScene.fusion_sources` keeps the last one) nothing is read back or synchronised until `PointCloud.trim()`.
+        Like `render_path` the CNNs run in train() as validation runs them, and the model is left as found: every buffer of the consistency
+        learner and every module's `training` flag is restored, also when a frame raises."""
+        from .fusion import fuse_views
+        if depth_source not in ("render", "mvs"):
+            raise ValueError("UCNeRFSystem.reconstruct: depth_source must be 'render' or 'mvs', got %r" % (depth_source,))
+        frames = list(range(scene.N)) if frames is None else [int(f) for f in frames]
+        if not frames or min(frames) < 0 or max(frames) >= scene.N:
+            raise IndexError("UCNeRFSystem.reconstruct: frames %r outside 0..%d (or empty)" % (frames, scene.N - 1))
+        n_views, n_src = int(self.args.view_num), int(n_src)
+        dev, P, H, W = scene.frames.device, len(frames), scene.H, scene.W
+        depth, rgb = torch.empty(P, H, W, device=dev), torch.empty(P, 3, H, W, device=dev)
+        conf = torch.empty(P, H, W, device=dev) if depth_source == "mvs" else None
+        net = self.Consist_Learner
+        flags = [(m, m.training) for n in (net, self.render_kwargs_train['network_fn']) for m in n.modules()]
+        with torch.no_grad():
+            saved = [(b, b.clone()) for b in net.buffers()]
+            try:
+                net.train()
+                for j, f in enumerate(frames):
+                    batch = scene.sample(f, scene.nearest_train_views(f, n_views), unpreprocess=True)
+                    d, c, q = self._frame_maps(batch, depth_source)
+                    depth[j].copy_(d)
+                    rgb[j].copy_(c)
+                    if conf is not None:
+                        conf[j].copy_(q)
+            finally:
+                for b, was in saved:
+                    b.copy_(was)
+                for m, was in flags:
+                    m.training = was
+            c2ws, w2cs = torch.stack([scene.c2w[f] for f in frames]), torch.stack([scene.w2c[f] for f in frames])
+            K = torch.stack([scene.intrinsic[f] for f in frames])
+            return fuse_views(depth, rgb, K, c2ws, src_ids=scene.fusion_sources(frames, n_src), w2cs=w2cs, conf=conf, **thresholds)
+
     # ------------------------------------------------------------------------------------------------ train.py:326-402
     def on_validation_epoch_end(self):
         """-> {'val/PSNR', 'val/SSIM', 'val/LPIPS', 'val/abs_rel', 'val/sq_rel', 'val/rmse', 'val/rmse_log', 'val/a1', 'val/a2', 'val/a3'}; with
